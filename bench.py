@@ -8,11 +8,17 @@ N > 1: one process per GPU (torchrun), one all-reduce of the flat gradient buffe
 with the backward), 1/world folded into the SGD kernel.  `--scaling weak` (default, what the driver runs): per-GPU batch fixed;
 `--scaling strong`: the GLOBAL batch is fixed (256 by default, `--batch` = global) and every rank takes batch // N -- the reference's own
 per-rank batch rule (core/trainer.py:229-241) and SURVEY.md section 8(d)'s first series.  With N > 1 the line carries a `dp` object:
-backend, exchange, and per rank the step time plus a breakdown measured in a separate instrumented pass AFTER the timed region
+backend, exchange, and per rank the step time, with `--full` plus a breakdown measured in a separate instrumented pass AFTER the timed region
 (backward, exposed exchange = what the stream still waits for once the backward is done, optimizer, the bucket's all-reduce alone).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, timed live with HIP events) and
-`cpu_baseline` (the CPU oracle of the same step on the host cores, bounded sample) objects.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`) with the figures derived from it; with N > 1 the `dp` object carries the per-rank record.
+`--full` adds what takes runs of its own: `roofline` (dominant kernel, timed live with HIP events, before the timed region), the `dp`
+step breakdown, the `secondary` lines of the other BASELINE workloads and `cpu_baseline` (the CPU oracle of the same step on the host
+cores, bounded sample).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all): the last
+step's loss and accuracy and the state the step hands back -- every parameter the optimizer updates and the floating-point buffers
+(BatchNorm running statistics) -- or, for the per-task passes, the Fisher diagonal / the herding picks.  The inputs are seeded.
 """
 import argparse
 import json
@@ -53,8 +59,10 @@ def parse():
                              # the single-GPU per-task work north_star names (a "step" = one batch of the Fisher pass / one class of the herding)
                              "ewc_fisher_pass", "herding_b50"])
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the live lines of the other BASELINE workloads behind the headline")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline kernels, the dp step breakdown, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the live lines of the other BASELINE workloads behind the headline")
     ap.add_argument("--roofline-only", action="store_true", help="run only the roofline kernels' launches (what the PMC passes sample) and print their block")
     ap.add_argument("--cpu-steps", type=int, default=None, help="steps of the CPU baseline sample (default: 5 ResNet, 1-2 ViT)")
     return ap.parse_args()
@@ -141,6 +149,68 @@ def synthetic_batch(B, lo, hi, seed, dev, size=32):
     x = (x - mean) / std
     y = torch.randint(lo, hi, (B,), generator=g)
     return {"image": x.to(dev), "label": y.to(dev)}
+
+
+DUMP_MAX_BYTES = 64_000_000        # --dump-outputs: all files together
+
+
+class LastValueMeter:
+    """the AverageMeter train_steps updates, keeping the last value of every key (the last step's loss / accuracy, still on the device)"""
+
+    def __init__(self, meter):
+        self.meter, self.last = meter, {}
+
+    def update(self, key, value, n=1):
+        self.last[key] = value
+        self.meter.update(key, value, n)
+
+    def avg(self, key):
+        return self.meter.avg(key)
+
+
+def _scalar(v):
+    """a meter value (0-dim tensor, ops.Deferred or number) as float64 [1], read after the timed region"""
+    if torch.is_tensor(v):
+        return v.detach().double().reshape(1).cpu()
+    if hasattr(v, "tensor"):
+        return (v.tensor.detach().double().reshape(()) * v.scale).reshape(1).cpu()
+    return torch.tensor([float(v)], dtype=torch.float64)
+
+
+def step_outputs(model, opt, last):
+    """what a caller of train_steps holds after its last step: that step's loss and accuracy, every parameter the optimizer updates
+    (param_groups order, flattened) and the model's floating-point buffers (BatchNorm running statistics)"""
+    out = {"loss": _scalar(last["loss"]), "acc1": _scalar(last["acc1"])}
+    seen, params = set(), []
+    for group in opt.param_groups:
+        for p in group["params"]:
+            if id(p) not in seen:
+                seen.add(id(p))
+                params.append(p.detach().reshape(-1).float())
+    out["params"] = torch.cat(params)
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()] if hasattr(model, "named_buffers") else []
+    if bufs:
+        out["buffers"] = torch.cat(bufs)
+    return out
+
+
+def dump_outputs(d, arrays):
+    """arrays (name -> tensor) -> d/<name>.npy, float64 kept, everything else float32.  Above DUMP_MAX_BYTES in all, every array of more
+    than 1 MB is cut to the same fraction of its elements, a fixed sample (positions drawn by numpy's default_rng(0), in increasing order)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu()
+        out[k] = v.numpy() if v.dtype == torch.float64 else v.float().numpy()
+    big = {k: a for k, a in out.items() if a.nbytes > 1 << 20}
+    room = DUMP_MAX_BYTES - 1024 * len(out) - sum(a.nbytes for k, a in out.items() if k not in big)      # (1 KB per file for the .npy header)
+    total = sum(a.nbytes for a in big.values())
+    if total > room:
+        for k, a in big.items():
+            out[k] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, a.size * room // total, replace=False))]
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _physical_cores():
@@ -604,7 +674,7 @@ def task_work_main(a):
     bb = M.cifar_resnet32(dtype=a.dtype)
     if fisher:
         B = a.batch or 32                                                  # config/ewc-resnet32-cifar100-b50-5-10.yaml: batch_size 32
-        steps, warm = a.steps or 200, a.warmup if a.warmup is not None else 20
+        steps, warm = a.steps if a.steps is not None else 200, a.warmup if a.warmup is not None else 20
         m = M.EWC(bb, 64, 100, device=dev, init_cls_num=50, inc_cls_num=5, lamda=1000).to(dev)
         m.before_task(0, None, None, None)
         batches = [synthetic_batch(B, 0, 50, 100 + i, dev) for i in range(4)]
@@ -620,7 +690,7 @@ def task_work_main(a):
         metric = "images/sec (EWC Fisher pass after task 0: 25000 images), CIFAR-100 B50-5x10"
     else:
         B = a.batch or 500                                                   # images of one class
-        steps, warm = a.steps or 50, a.warmup if a.warmup is not None else 50       # a "step" = one class; the default is one task's 50 classes
+        steps, warm = a.steps if a.steps is not None else 50, a.warmup if a.warmup is not None else 50       # a "step" = one class; the default is one task's 50 classes
         net = M.ICarl(bb, 64, 100, device=dev, init_cls_num=50, inc_cls_num=5, task_num=11).to(dev)
         net.before_task(0, None, None, None)
         net.eval()
@@ -642,10 +712,21 @@ def task_work_main(a):
     run(warm)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(steps)
+    res = run(steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ips = per_step_imgs * steps / dt
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dict(zip(("fisher_flat", "fisher_head_w", "fisher_head_b"), res)) if fisher else
+                     {"exemplars": torch.stack(res).double()})
+    step_flops = 3 * FLOP_FWD_PER_IMG["cifar_resnet32"] if fisher else FLOP_FWD_PER_IMG["cifar_resnet32"]
+    out = {"metric": metric, "value": ips, "unit": "images/sec", "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32" if fisher else a.dtype, "data": "synthetic", "config": desc,
+           "whole_pass_seconds": (25000.0 / ips), "step_tflops_algorithmic": step_flops * ips / 1e12,
+           "step_frac_of_hbm_peak": (HBM_BYTES_STEP_PER_IMG["cifar_resnet32"] * (2.0 if fisher else 0.4)) * ips / 1e9 / PEAK_HBM_GBS}
+    if not a.full:
+        print(json.dumps(out))
+        return
     # roofline of the pass's own elementwise / selection kernel, timed live (the convolution kernels are priced by the training workloads)
     st = torch.cuda.current_stream().cuda_stream
     if fisher:
@@ -656,7 +737,6 @@ def task_work_main(a):
         roof = dict(bound="hbm", kernel=f"fisher_accum_kernel: f += s * g^2 over the flat parameter buffer ({flat.numel()} fp32)", launch_ms=ms, algorithmic_bytes_per_launch=nbytes,
                     achieved=nbytes / (ms * 1e-3) / 1e9, peak=PEAK_HBM_GBS, unit="GB/s", frac=nbytes / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, traffic=None,
                     note="5.6 MB per launch: a launch at its latency floor, not a bandwidth-bound one")
-        step_flops = 3 * FLOP_FWD_PER_IMG["cifar_resnet32"]
     else:
         cf = ops.l2_normalize_rows(torch.randn(B, 64, device=dev))
         cf = ops.l2_normalize_rows(torch.randn(50 * B, 64, device=dev))
@@ -665,12 +745,7 @@ def task_work_main(a):
         roof = dict(bound="hbm", kernel=f"herding_batched_kernel: 50 classes x 40 greedy picks over [{B}, 64] normalised features, one workgroup per class", launch_ms=ms,
                     algorithmic_bytes_per_launch=nbytes, achieved=nbytes / (ms * 1e-3) / 1e9, peak=PEAK_HBM_GBS, unit="GB/s", frac=nbytes / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
                     traffic=None, note="40 sequential picks per class on LDS-resident rows: latency-bound by construction (50 workgroups; 6.4 MB read once)")
-        step_flops = FLOP_FWD_PER_IMG["cifar_resnet32"]
-    out = {"metric": metric, "value": ips, "unit": "images/sec", "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f32" if fisher else a.dtype, "data": "synthetic", "config": desc,
-           "whole_pass_seconds": (25000.0 / ips), "step_tflops_algorithmic": step_flops * ips / 1e12,
-           "step_frac_of_hbm_peak": (HBM_BYTES_STEP_PER_IMG["cifar_resnet32"] * (2.0 if fisher else 0.4)) * ips / 1e9 / PEAK_HBM_GBS,
-           "roofline": roof}
+    out["roofline"] = roof
     print(json.dumps(out))
 
 
@@ -748,19 +823,20 @@ def main():
     model.train()
     batches = [synthetic_batch(a.batch, lo, hi, 100 + rank * 7 + i, dev, 224 if vit else 32) for i in range(4)]
     name = type(model).__name__
-    meter = AverageMeter("train", ["loss", "acc1"])
+    meter = LastValueMeter(AverageMeter("train", ["loss", "acc1"]))
 
     def run(n):
         train_steps(model, opt, (batches[i % len(batches)] for i in range(n)), reducer, name, meter, dev)
 
-    # the dominant kernel's roofline measurement (HIP events around repeated launches of that kernel alone) runs first: it is
+    # --full: the dominant kernel's roofline measurement (HIP events around repeated launches of that kernel alone) runs first: it is
     # independent of the step, and the GPU enters the timed region at its sustained clocks instead of waking up in it
-    more = []
-    if vit:
-        roofline = gemm_roofline(dev, a.dtype, a.batch * (222 if a.workload.startswith("l2p") else 197), a.workload, a.batch == (16 if a.workload.startswith("l2p") else 128))
-    else:
-        rl = conv_rooflines(dev, a.dtype, a.batch, a.workload)
-        roofline, more = rl[0], rl[1:]
+    roofline, more = None, []
+    if a.full or a.roofline_only:
+        if vit:
+            roofline = gemm_roofline(dev, a.dtype, a.batch * (222 if a.workload.startswith("l2p") else 197), a.workload, a.batch == (16 if a.workload.startswith("l2p") else 128))
+        else:
+            rl = conv_rooflines(dev, a.dtype, a.batch, a.workload)
+            roofline, more = rl[0], rl[1:]
     if a.roofline_only:               # the launches the PMC passes of tools/bench_profile.py sample
         if rank == 0:
             print(json.dumps(dict(roofline=roofline, roofline_more=more)))
@@ -784,11 +860,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_avg = meter.avg("loss")
+    if a.dump_outputs and rank == 0:
+        assert a.steps > 0, "--dump-outputs needs at least one timed step"
+        dump_outputs(a.dump_outputs, step_outputs(model, opt, meter.last))
     dp = None
     if world > 1:            # self-checking record of the process group: one entry per rank, gathered over the collective backend itself
         mine = dict(rank=rank, local_rank=local, device=torch.cuda.get_device_name(local), pci=torch.cuda.get_device_properties(local).pci_bus_id
                     if hasattr(torch.cuda.get_device_properties(local), "pci_bus_id") else None, ms_per_step=dt / a.steps * 1e3)
-        mine.update(dp_breakdown(model, opt, reducer, batches, name, dev))
+        if a.full:
+            mine.update(dp_breakdown(model, opt, reducer, batches, name, dev))
         every = [None] * world
         dist.all_gather_object(every, mine)
         import libcontinual_amd
@@ -825,6 +905,9 @@ def main():
         out["step_bound"] = "hbm" if arch == "cifar_resnet32" else "mfma"
     if dp is not None:
         out["dp"] = dp
+    if not a.full:
+        print(json.dumps(out))
+        return
     meta = _profile_meta(a.workload)
     if meta is not None and isinstance(roofline, dict):
         cur = _src_hash()

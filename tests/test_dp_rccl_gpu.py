@@ -87,7 +87,7 @@ def test_two_gpus_train_in_lockstep_over_rccl(tmp_path, exchange):
 def test_bench_over_rccl_reports_the_overlap(scaling):
     """bench.py --gpus 2 on two devices: backend nccl, and the exposed part of the exchange (what the compute stream still waits for after
     the backward) is shorter than the bucket's all-reduce alone -- the tail handed over early ran under the backward"""
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5", "--scaling", scaling, "--no-cpu-baseline"])
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5", "--scaling", scaling, "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     dp = out["dp"]

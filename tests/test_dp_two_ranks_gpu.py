@@ -142,7 +142,7 @@ def test_bench_strong_scaling_and_step_breakdown_at_two_ranks():
     """`--scaling strong`: the GLOBAL batch is fixed and every rank takes batch // N (core/trainer.py:229-241); the `dp` object carries
     the per-rank breakdown of the step (backward, exposed exchange, optimizer, the bucket's all-reduce alone) that makes a SCALE record
     self-diagnosing"""
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--scaling", "strong", "--no-cpu-baseline"])
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--scaling", "strong", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 64 and out["config"]["per_gpu_batch"] == 32
@@ -178,7 +178,7 @@ def test_bench_icarl_strong_scaling_at_eight_ranks(exchange):
     step -- with the ragged reduce-scatter shards of a 466 256-element buffer (n % 32 = 16) in the second form; ONE json line, whole-job rate,
     one `dp` entry per rank with the step breakdown"""
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "2", "--workload", "icarl_resnet32_b50_task1", "--batch", "256",
-                 "--scaling", "strong", "--no-cpu-baseline"], timeout=900, nproc=8, OMP_NUM_THREADS="1", CLHIP_DP_EXCHANGE=exchange)
+                 "--scaling", "strong", "--full", "--no-cpu-baseline"], timeout=900, nproc=8, OMP_NUM_THREADS="1", CLHIP_DP_EXCHANGE=exchange)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
