@@ -59,6 +59,10 @@ int clhip_conv_weight_prep(const float* w, void* w_fwd, void* w_dg, int K, int t
  * Convolution as implicit GEMM on MFMA (replaces nn.Conv2d fwd / dgrad / wgrad, reference
  * backbone/resnet.py:17-24, 295-298, 337, 367).  ksize in {1,3}; C, K multiples of 8 (pad the
  * 3-channel stem to 8); H,W arbitrary.  Ho = (H + 2*pad - ksize)/stride + 1.
+ * ksize 7 (fwd, wgrad and their sizing queries only): the ImageNet stem conv1 = Conv2d(3, 64, 7, stride 2, pad 3)
+ * (resnet.py:136-137) with C == 8 (padded), stride 2, pad 3, K in {16, 32, 64}, both dtypes; the forward takes the
+ * statistics through stat_acc only (stat_partials must be NULL) and the weight gradient needs `ws` (deterministic
+ * partial blocks).  Any other 7x7 call, and every 7x7 dgrad, returns CLHIP_EINVAL.
  *
  * fwd : z[N,Ho,Wo,K] = conv(x[N,H,W,C], w_fwd).  If stat_partials != NULL it receives per-tile
  *       partial sums for train-mode BatchNorm: float[tiles][2][K] (sum, sum of squares of the fp32
@@ -169,6 +173,23 @@ int clhip_avgpool_bwd_bn_reduce_supported(int N, int HW, int C, int dtype);
 int clhip_avgpool_bwd_bn_reduce(const float* dfeat, void* da, const void* z_prod, const void* y_prod /*nullable*/, const float* mean, const float* invstd,
                                 double* acc, int replicas, int N, int HW, int C, int dtype, void* stream);
 
+/* The ImageNet stem's BatchNorm -> ReLU -> MaxPool2d(kernel_size=3, stride=2, padding=1) (reference resnet.py:138-149, 217-218), fused.
+ * clhip_maxpool_out_dim(H) = (H - 1) / 2 + 1 (nn.MaxPool2d's floor rule for these settings).
+ * fwd: z [N,H,W,C] (the stem conv's raw output) -> y [N,Hp,Wp,C] = maxpool(relu(bn(z))) and argmax [N,Hp,Wp,C] uint8 (nullable) = the window position
+ *   (ky * 3 + kx, row-major from the top-left corner at (2 hp - 1, 2 wp - 1)) of the first maximum -- torch's `val > maxval` rule: ties go to the
+ *   earliest position, padding never wins.  training != 0: batch statistics from stat_acc [replicas][2][C] (the conv's sums, as clhip_bn_apply_train),
+ *   mean / invstd saved, running statistics updated when non-NULL; training == 0: running statistics (nn.BatchNorm2d eval), stat_acc / mean / invstd
+ *   ignored.  C a power of two in [8, 2048].
+ * bwd (gather form, no atomics on the tensor): g [N,H,W,C] = (bn(z) > 0) * sum of dy [N,Hp,Wp,C] over the <= 4 pooled outputs whose argmax is
+ *   the pixel (MaxPool2d + ReLU backward), and the two BatchNorm-backward sums (sum g, sum g * xhat) ADDED into acc [replicas][2][C] as
+ *   clhip_conv_dgrad_bn_reduce does: clhip_bn_bwd_apply_acc(relu = 0) on g then forms dz. */
+int clhip_maxpool_out_dim(int H);
+int clhip_bn_relu_maxpool_fwd(const void* z, const double* stat_acc, int replicas, const float* gamma, const float* beta, float* running_mean,
+                              float* running_var, float momentum, float eps, float* mean, float* invstd, void* y, void* argmax /*nullable*/, int N, int H,
+                              int W, int C, int training, int dtype, void* stream);
+int clhip_maxpool_bwd_bn_reduce(const void* dy, const void* argmax, const void* z, const float* mean, const float* invstd, const float* gamma,
+                                const float* beta, void* g, double* acc, int replicas, int N, int H, int W, int C, int dtype, void* stream);
+
 /* AvgPool2d(win) + NCHW flatten: feat[n][(c*Ph + ph)*Pw + pw] (fp32), Ph = H/win, Pw = W/win (resnet.py:643, 675-676) */
 int clhip_avgpool_win_fwd(const void* a, float* feat, int N, int H, int W, int C, int win, int dtype, void* stream);
 int clhip_avgpool_win_bwd(const float* dfeat, void* da, int N, int H, int W, int C, int win, int dtype, void* stream);
@@ -192,7 +213,11 @@ enum {
     CLHIP_UNIT_RELU = 1,     /* ReLU after the BatchNorm (+ residual)                                                                 */
     CLHIP_UNIT_PRE_RES = 2,  /* `res` names a unit whose raw (pre-BatchNorm) sum is added to this conv's output BEFORE the BatchNorm  */
     CLHIP_UNIT_RAW_SRC = 4,  /* the conv reads the raw sum of activation `src` instead of its normalised output                       */
-    CLHIP_UNIT_NO_BN = 8     /* conv only (gamma/beta/rm/rv offsets ignored); the result is consumed through PRE_RES / RAW_SRC         */
+    CLHIP_UNIT_NO_BN = 8,    /* conv only (gamma/beta/rm/rv offsets ignored); the result is consumed through PRE_RES / RAW_SRC         */
+    CLHIP_UNIT_MAXPOOL = 16  /* the ImageNet stem (resnet.py:136-149, 217-218): conv -> BN -> ReLU -> MaxPool2d(3, 2, 1).  Unit 0 only, src 0,
+                                RELU set, no residual; activation 1 is the pooled map (z and the argmax map stay in the workspace).  This unit
+                                may also be 7x7 / stride 2 / pad 3 (Cin <= 8); a 7x7 unit without this bit is refused.  Training needs the
+                                accumulator path (the default).                                                                        */
 };
 
 typedef struct {

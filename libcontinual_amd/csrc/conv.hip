@@ -476,6 +476,11 @@ int clhip_wgrad3_launch(const void* x, const void* dz, float* dw, float* ws, int
 size_t clhip_wgrad3_ws_bytes(int N, int H, int W, int C, int K);
 bool clhip_stem_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype);
 int clhip_stem_launch(const void* x, const void* w, void* z, double* acc, int rep, int N, int H, int W, int K, hipStream_t st);
+bool clhip_stem7_supported(int N, int H, int W, int C, int K, int stride, int pad);                                   // stem7.hip (7x7 / s2 / p3)
+int clhip_stem7_fwd_tiles(int N, int H, int W);
+int clhip_stem7_fwd_launch(const void* x, const void* w, void* z, double* acc, int rep, int N, int H, int W, int K, int dtype, hipStream_t st);
+size_t clhip_stem7_wgrad_ws_bytes(int N, int H, int W, int Creal, int K, int dtype);
+int clhip_stem7_wgrad_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int Creal, int K, int dtype, hipStream_t st);
 bool clhip_shortcut_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype);
 int clhip_shortcut_dgrad(const void* dz, const void* w_dg, void* dx, int accumulate, int N, int H, int W, int C, int K, hipStream_t st);
 bool clhip_stem_wgrad_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
@@ -505,6 +510,7 @@ static bool use_v1() {
 extern "C" int clhip_conv_fwd_tiles(int N, int H, int W, int C, int K, int ksize, int stride, int pad) {
     int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
     int M = N * Ho * Wo;
+    if (ksize == 7) return clhip_stem7_supported(N, H, W, C, K, stride, pad) ? clhip_stem7_fwd_tiles(N, H, W) : 0;      // (workgroups; no partial rows)
     // NB: the plan sizes the statistics scratch with this; dtype is not known here, so report the larger count
     if (!use_v1()) {
         int t2 = clhip_conv2_tiles_m(M, K);
@@ -541,6 +547,12 @@ extern "C" int clhip_conv_fwd_acc(const void* x, const void* w_fwd, void* z, dou
 
 static int conv_fwd_impl(const void* x, const void* w_fwd, void* z, float* stat_partials, double* stat_acc, int stat_rep, int N, int H, int W, int C,
                          int K, int ksize, int stride, int pad, int dtype, void* stream) {
+    if (ksize == 7) {
+        // the ImageNet stem (<= 8 padded input channels, stride 2, pad 3): stem7.hip, both dtypes; statistics through the accumulators only
+        CLHIP_CHECK_ARG(clhip_stem7_supported(N, H, W, C, K, stride, pad) && x && w_fwd && z && stat_partials == nullptr);
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        return clhip_stem7_fwd_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, dtype, static_cast<hipStream_t>(stream));
+    }
     if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
     CLHIP_CHECK_ARG(x && w_fwd && z);
     CLHIP_CHECK_ARG(!(stat_acc && use_v1()));
@@ -927,6 +939,7 @@ extern "C" int clhip_conv_dgrad_pair_bn_reduce(const void* dz, const void* w_pac
 }
 
 extern "C" size_t clhip_conv_wgrad_ws_bytes(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
+    if (ksize == 7) return clhip_stem7_supported(N, H, W, C, K, stride, pad) ? clhip_stem7_wgrad_ws_bytes(N, H, W, Creal, K, dtype) : 0;
     size_t b = wgrad_ws_bytes_single(N, H, W, C, Creal, K, ksize, stride, pad, dtype);
     if (!use_v1() && use_v3() && Creal == C && stride == 2 && clhip_wgrad7_supported(N, H, W, C, K, dtype)) {
         if (ksize == 3 && pad == 1) b = std::max(b, clhip_wgrad7_ws_bytes(N, C, K, 0));
@@ -948,6 +961,12 @@ static size_t wgrad_ws_bytes_single(int N, int H, int W, int C, int Creal, int K
 
 extern "C" int clhip_conv_wgrad(const void* x, const void* dz, float* dw, void* ws, int N, int H, int W, int C, int Creal, int K,
                                 int ksize, int stride, int pad, int dtype, void* stream) {
+    if (ksize == 7) {
+        // stem7.hip: partial blocks + fixed-order reduce (the scratch is required: there is no atomic form)
+        CLHIP_CHECK_ARG(clhip_stem7_supported(N, H, W, C, K, stride, pad) && x && dz && dw && ws && Creal >= 1 && Creal <= C && (K * 49 * Creal) % 4 == 0);
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        return clhip_stem7_wgrad_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, Creal, K, dtype, static_cast<hipStream_t>(stream));
+    }
     if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
     CLHIP_CHECK_ARG(x && dz && dw && Creal >= 1 && Creal <= C);
     WgradParams p;

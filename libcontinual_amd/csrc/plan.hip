@@ -86,6 +86,8 @@ struct Unit {
     int rep_fwd, rep_bwd;                        // accumulator replicas (power of two): ~64 producer workgroups per replica
     int dx_acc, dres_acc;
     bool relu, pre_res, raw_src, no_bn;          // decoded CLHIP_UNIT_* bits of d.relu
+    bool maxpool;                                // CLHIP_UNIT_MAXPOOL (unit 0 of the ImageNet stem): BN -> ReLU -> 3x3 / s2 max-pool; its activation is the pooled map
+    size_t am_off, pg_off;                       // ... its argmax map [N,Hp,Wp,C] (uint8) and the full-size gradient of the max-pool's input (bytes into the workspace)
     bool has_dzr;                                // this unit's raw sum is consumed raw (PRE_RES / RAW_SRC) by a later unit
     size_t dzr_off;                              // ... whose gradient contribution lands here (bytes into the workspace)
     size_t mask_off;                             // packed ReLU mask of a conv -> BN -> +res -> ReLU unit (bytes into the workspace; 0: none)
@@ -193,9 +195,14 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
         u.d = units[i];
         u.relu = (u.d.relu & CLHIP_UNIT_RELU) != 0; u.pre_res = (u.d.relu & CLHIP_UNIT_PRE_RES) != 0;
         u.raw_src = (u.d.relu & CLHIP_UNIT_RAW_SRC) != 0; u.no_bn = (u.d.relu & CLHIP_UNIT_NO_BN) != 0;
-        if (u.d.src < 0 || u.d.src > i || u.d.res > i || (u.d.ksize != 1 && u.d.ksize != 3) || u.d.stride < 1 || u.d.cout % 16 ||
+        u.maxpool = (u.d.relu & CLHIP_UNIT_MAXPOOL) != 0;
+        // the ImageNet stem (unit 0 only): the max-pool behind its ReLU, and a 7x7 / s2 / p3 convolution of the (<= 8 padded channels) network input,
+        // which is legal only together with that max-pool
+        const bool stem7 = u.d.ksize == 7 && u.maxpool && i == 0 && u.d.src == 0 && p->Cin_pad == 8 && u.d.stride == 2 && u.d.pad == 3;
+        if (u.d.src < 0 || u.d.src > i || u.d.res > i || (u.d.ksize != 1 && u.d.ksize != 3 && !stem7) || u.d.stride < 1 || u.d.cout % 16 ||
             (u.raw_src && u.d.src < 1) || (u.pre_res && u.d.res < 1) || (u.no_bn && (u.pre_res || u.relu || u.d.res >= 0)) ||
-            (u.d.relu & ~(CLHIP_UNIT_RELU | CLHIP_UNIT_PRE_RES | CLHIP_UNIT_RAW_SRC | CLHIP_UNIT_NO_BN))) {
+            (u.maxpool && (i != 0 || u.d.src != 0 || !u.relu || u.d.res >= 0 || u.pre_res || u.raw_src || u.no_bn)) ||
+            (u.d.relu & ~(CLHIP_UNIT_RELU | CLHIP_UNIT_PRE_RES | CLHIP_UNIT_RAW_SRC | CLHIP_UNIT_NO_BN | CLHIP_UNIT_MAXPOOL))) {
             clhip_set_error("clhip_plan_create: bad unit %d", i);
             delete p;
             return nullptr;
@@ -222,9 +229,19 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
         }
         size_t bytes = (size_t)u.M * u.d.cout * p->esize;
         u.z_off = off; off = align_up(off + bytes);
-        Act a{u.Ho, u.Wo, u.d.cout, off, 0, bytes};
-        off = align_up(off + bytes);
-        p->acts.push_back(a);
+        if (u.maxpool) {
+            const int Hp = clhip_maxpool_out_dim(u.Ho), Wp = clhip_maxpool_out_dim(u.Wo);
+            const size_t pooled = (size_t)N * Hp * Wp * u.d.cout;
+            Act a{Hp, Wp, u.d.cout, off, 0, pooled * p->esize};
+            off = align_up(off + a.bytes);
+            p->acts.push_back(a);
+            u.am_off = off; off = align_up(off + pooled);
+            u.pg_off = off; off = align_up(off + bytes);
+        } else {
+            Act a{u.Ho, u.Wo, u.d.cout, off, 0, bytes};
+            off = align_up(off + bytes);
+            p->acts.push_back(a);
+        }
         size_t wbytes = (size_t)u.d.cout * u.d.ksize * u.d.ksize * u.cin_pad * p->esize;
         u.sh_fwd = sh; sh = align_up(sh + wbytes);
         u.sh_dg = sh; sh = align_up(sh + wbytes);
@@ -246,6 +263,11 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
             off = align_up(off + (size_t)u.M * u.d.cout / 8);
         }
         if (u.no_bn) u.rep_fwd = u.rep_bwd = 0;
+        if (u.maxpool && (u.rep_fwd <= 0 || u.rep_bwd <= 0)) {
+            clhip_set_error("clhip_plan_create: unit %d: the max-pool stem needs the BatchNorm accumulator path (CLHIP_BN_PARTIALS unset)", i);
+            delete p;
+            return nullptr;
+        }
         u.a_fwd = ndouble; ndouble += 2 * (size_t)u.d.cout * (u.rep_fwd > 0 ? u.rep_fwd : 1);
         u.a_bwd = ndouble; ndouble += 2 * (size_t)u.d.cout * (u.rep_bwd > 0 ? u.rep_bwd : 1);
         if (u.rep_fwd || u.rep_bwd) p->use_acc = true;
@@ -276,7 +298,7 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
         }
         if (n_cons != 1 || consumer <= b || p->units[consumer].pre_res || p->units[consumer].rep_fwd <= 0 || p->units[consumer].rep_bwd <= 0) continue;
         Unit& prod = p->units[u.d.src - 1];
-        if (prod.no_bn || prod.rep_fwd <= 0 || prod.forks >= 0 || p->units[consumer].joins >= 0) continue;
+        if (prod.no_bn || prod.maxpool || prod.rep_fwd <= 0 || prod.forks >= 0 || p->units[consumer].joins >= 0) continue;
         u.branch = p->n_branch; prod.forks = p->n_branch; p->units[consumer].joins = p->n_branch;
         ++p->n_branch;
         size_t wg = clhip_conv_wgrad_ws_bytes(N, u.H, u.W, u.cin_pad, u.d.cin, u.d.cout, u.d.ksize, u.d.stride, u.d.pad, dtype);
@@ -380,7 +402,7 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
         if ((long long)u.M > fuse_max_m && !clhip_conv_dgrad_bn_reduce_overlapped(N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize, u.d.stride, u.d.pad, dtype)) continue;
         const int a = u.d.src;                      // the activation; produced by unit a - 1
         const Unit& prod = p->units[a - 1];
-        if (prod.no_bn || prod.pre_res || prod.raw_src || prod.has_dzr || prod.rep_bwd <= 0) continue;
+        if (prod.no_bn || prod.pre_res || prod.raw_src || prod.has_dzr || prod.rep_bwd <= 0 || prod.maxpool) continue;
         bool lowest = true;
         for (int k = 0; k < n_units; ++k) {
             if (k == i) continue;
@@ -418,7 +440,7 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
         // (own scratch regions per unit -- the deferred-reduce plans -- so that both partial-block slabs survive until the one reduce launch)
         {
             const Unit& prod = p->units[ua.d.src - 1];       // users == 2: the pair's launch is the only writer of that activation's gradient
-            ua.pair_fuse_bn = fuse_on && !prod.no_bn && !prod.pre_res && !prod.raw_src && !prod.has_dzr && prod.rep_bwd > 0 && (long long)prod.M <= fuse_max_m &&
+            ua.pair_fuse_bn = fuse_on && !prod.no_bn && !prod.maxpool && !prod.pre_res && !prod.raw_src && !prod.has_dzr && prod.rep_bwd > 0 && (long long)prod.M <= fuse_max_m &&
                               clhip_conv_dgrad_pair_bn_reduce_supported(N, ua.H, ua.W, ua.cin_pad, ua.d.cout, dtype) != 0;
         }
         ua.fpair = ub.fpair = ua.rep_fwd > 0 && ub.rep_fwd > 0 && ua.cin_pad == ua.d.cin &&
@@ -435,7 +457,8 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
     static const bool mask_y = clhip_cfg("BN_MASK_FROM_Y") != nullptr;
     for (int a = 0; a + 1 < n_units && want_acc && !mask_y; ++a) {
         Unit& ua = p->units[a];
-        if (!ua.relu || ua.d.res >= 0 || ua.pre_res || ua.no_bn || ua.has_dzr || ua.rep_fwd <= 0 || ua.rep_bwd <= 0 || ua.mask_off != 0 || ua.branch >= 0 || ua.forks >= 0) continue;
+        if (!ua.relu || ua.d.res >= 0 || ua.pre_res || ua.no_bn || ua.has_dzr || ua.rep_fwd <= 0 || ua.rep_bwd <= 0 || ua.mask_off != 0 || ua.branch >= 0 || ua.forks >= 0 ||
+            ua.maxpool) continue;
         int b = -1, users = 0;
         for (int k = 0; k < n_units; ++k) {
             const Unit& o = p->units[k];
@@ -479,7 +502,8 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
     p->wt_pending.assign(p->units.size(), 0);
     for (int a = 0; a + 1 < n_units && want_acc && !mask_y; ++a) {
         Unit& ua = p->units[a];
-        if (!ua.relu || ua.pre_res || ua.no_bn || ua.has_dzr || ua.raw_src || ua.rep_fwd <= 0 || ua.branch >= 0 || ua.forks >= 0 || ua.lazy_to >= 0 || ua.res_lazy_to >= 0) continue;
+        if (!ua.relu || ua.pre_res || ua.no_bn || ua.has_dzr || ua.raw_src || ua.rep_fwd <= 0 || ua.branch >= 0 || ua.forks >= 0 || ua.lazy_to >= 0 || ua.res_lazy_to >= 0 ||
+            ua.maxpool) continue;
         if (ua.d.res >= 0 && ua.mask_off == 0) continue;
         int b = -1;
         bool ok = true;
@@ -1067,6 +1091,14 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
             if (wt_on && u.wt_to >= 0 && !opens_run(u.wt_to)) { p->wt_pending[i] = 1; continue; }              // its first reader applies it in LDS and writes the activation [+ mask]
             if (lazy_on && u.lazy_to >= 0 && !opens_run(u.lazy_to)) { p->lazy_live[i] = 1; continue; }          // its one consumer applies the BatchNorm: no apply launch, no activation
             if (rlazy_on && u.res_lazy_to >= 0 && !opens_run(u.res_lazy_to)) { p->res_pending[i] = 1; continue; }   // its first consumer applies it and writes the activation + mask
+            if (u.maxpool) {
+                // the ImageNet stem: BatchNorm (batch statistics) + ReLU + 3x3 / s2 max-pool in one pass over z; the argmax map for the backward
+                // (training == 2: no backward follows, no argmax)
+                TRY(clhip_bn_relu_maxpool_fwd(ws + u.z_off, acc + u.a_fwd, u.rep_fwd, params + u.d.gamma_off, params + u.d.beta_off, bn_stats + u.d.rm_off,
+                                              bn_stats + u.d.rv_off, kBnMomentum, kBnEps, fr + u.f_mean, fr + u.f_invstd, ws + dst.y_off,
+                                              nosave ? nullptr : ws + u.am_off, p->N, u.Ho, u.Wo, u.d.cout, 1, p->dtype, us));
+                continue;
+            }
             const void* res_ = u.d.res >= 0 ? ws + p->acts[u.d.res].y_off : nullptr;
             if (plan_skip() & 1) continue;                       // timing ablation: no forward BatchNorm apply (results invalid)
             if (br_on && u.joins >= 0) (void)hipStreamWaitEvent((hipStream_t)stream, p->ev_join[u.joins], 0);      // the residual comes from the branch stream
@@ -1126,6 +1158,11 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
             } else {
                 TRY(clhip_conv_fwd(in, sh + u.sh_fwd, ws + u.z_off, nullptr, p->N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize, u.d.stride, u.d.pad, p->dtype, stream));
             }
+            if (u.maxpool) {
+                TRY(clhip_bn_relu_maxpool_fwd(ws + u.z_off, nullptr, 1, params + u.d.gamma_off, params + u.d.beta_off, bn_stats + u.d.rm_off, bn_stats + u.d.rv_off,
+                                              0.f, kBnEps, nullptr, nullptr, ws + dst.y_off, nullptr, p->N, u.Ho, u.Wo, u.d.cout, 0, p->dtype, stream));
+                continue;
+            }
             if (u.lazy_to >= 0 && !(stage_on && p->units[u.lazy_to].stage_len > 0)) { p->lazy_live[i] = 1; continue; }          // (a fused run reads a WRITTEN activation)
             if (u.res_lazy_to >= 0 && !(stage_on && p->units[u.res_lazy_to].stage_len > 0)) { p->res_pending[i] = 1; continue; }
             const void* res_e = u.d.res >= 0 ? ws + p->acts[u.d.res].y_off : nullptr;
@@ -1141,6 +1178,12 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
                                         fr + u.f_invstd, fr + u.f_scale, fr + u.f_shift, stream));
         }
         const void* res = u.d.res >= 0 ? ws + p->acts[u.d.res].y_off : nullptr;
+        if (u.maxpool) {                                          // (eval only: a max-pool plan always trains on the accumulator path)
+            if (training) { clhip_set_error("clhip_plan_forward: the max-pool stem trains on the accumulator path only"); return CLHIP_EINVAL; }
+            TRY(clhip_bn_relu_maxpool_fwd(ws + u.z_off, nullptr, 1, params + u.d.gamma_off, params + u.d.beta_off, bn_stats + u.d.rm_off, bn_stats + u.d.rv_off,
+                                          0.f, kBnEps, nullptr, nullptr, ws + dst.y_off, nullptr, p->N, u.Ho, u.Wo, u.d.cout, 0, p->dtype, stream));
+            continue;
+        }
         if (!training) {
             // eval mode: scale / shift of the running statistics are derived inside the apply launch (one launch per unit instead of two)
             TRY(clhip_bn_apply_eval(ws + u.z_off, params + u.d.gamma_off, params + u.d.beta_off, bn_stats + u.d.rm_off, bn_stats + u.d.rv_off, kBnEps, res, ws + dst.y_off,
@@ -1345,6 +1388,26 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
         const Unit& u = p->units[i];
         const Act& src = p->acts[u.d.src];
         const Act& dst = p->acts[i + 1];
+        if (u.maxpool) {
+            // the ImageNet stem: the max-pool's gather backward forms the ReLU-masked gradient of the BatchNorm output at full size and reduces the
+            // BatchNorm-backward sums on the way; the apply pass forms dz; the weight gradient reads the network input (no input gradient)
+            if (p->br_act >= 0) join_branch();
+            if (two_streams && any_pending()) {                  // the dz buffer and the weight-gradient scratch may still be read on the side stream
+                (void)hipEventRecord(p->ev_end, p->side);
+                (void)hipStreamWaitEvent(main_s, p->ev_end, 0);
+                clear_pending();
+            }
+            char* dz0 = ws + p->dz_off;
+            double* ab = reinterpret_cast<double*>(ws + p->acc_off) + u.a_bwd;
+            TRY(clhip_maxpool_bwd_bn_reduce(ws + dst.dy_off, ws + u.am_off, ws + u.z_off, fr + u.f_mean, fr + u.f_invstd, params + u.d.gamma_off, params + u.d.beta_off,
+                                            ws + u.pg_off, ab, u.rep_bwd, p->N, u.Ho, u.Wo, u.d.cout, p->dtype, stream));
+            TRY(clhip_bn_bwd_apply_acc(ws + u.pg_off, nullptr, ws + u.z_off, fr + u.f_mean, fr + u.f_invstd, params + u.d.gamma_off, params + u.d.beta_off,
+                                       grads + u.d.gamma_off, grads + u.d.beta_off, dz0, nullptr, 0, u.M, u.d.cout, 0, ab, u.rep_bwd, p->dtype, stream));
+            if (!(plan_skip() & 4))
+                TRY(clhip_conv_wgrad(ws + src.y_off, dz0, grads + u.d.w_off, ws + u.wg_own, p->N, u.H, u.W, u.cin_pad, u.d.cin, u.d.cout, u.d.ksize, u.d.stride,
+                                     u.d.pad, p->dtype, stream));
+            continue;
+        }
         void* dres = (u.d.res >= 0 && !u.pre_res) ? ws + p->acts[u.d.res].dy_off : nullptr;
         const bool pair_b = pair_on && u.pair >= 0 && u.d.ksize == 1 && u.pair == i - 1 && u.pair >= unit_lo;
         char* dz = ws + (two_streams ? p->dz_offs[k] : (pair_b ? p->dz_off2 : p->dz_off));
@@ -1564,6 +1627,10 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
 extern "C" int clhip_plan_read_act(clhip_plan* p, const void* workspace, int idx, int which, float* out_nchw, void* stream) {
     CLHIP_CHECK_ARG(p && workspace && out_nchw && idx >= 0 && idx < (int)p->acts.size() && which >= 0 && which <= 2);
     CLHIP_CHECK_ARG(!(idx == 0 && which != 0));
+    if (which == 1 && idx >= 1 && p->units[idx - 1].maxpool) {
+        clhip_set_error("clhip_plan_read_act: activation %d is the max-pooled stem output; its pre-pool z has another shape", idx);
+        return CLHIP_EINVAL;
+    }
     const char* ws = static_cast<const char*>(workspace);
     const Act& a = p->acts[idx];
     if (which == 0 && idx >= 1 && p->lazy_live[idx - 1]) {

@@ -134,7 +134,7 @@ def get_dataloader(config, mode, cls_map=None, device=None):
     if f"{mode}_trfms" in config:
         trfms = T.create_transforms(config[f"{mode}_trfms"])            # YAML-declared pipeline (dataloader.py:54-55)
     else:
-        trfms = T.cifar_resnet_transform(mode, config.get("image_size", 32))
+        trfms = T.default_transform(config, mode)                         # per-dataset defaults (dataloader.py:57-74)
     bs = config.get(f"{mode}_batch_size", config["batch_size"])
     if not config.get("gpu_input_pipeline", True):
         device = None

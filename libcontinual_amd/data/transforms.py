@@ -199,5 +199,32 @@ def cifar_resnet_transform(mode, size=32):
     return Compose(common)
 
 
+# the reference's per-dataset defaults (core/data/data.py:121-137, 191-211, selected by core/data/dataloader.py:40-74 when a config declares no
+# `*_trfms`): ImageNetRTransform keeps the CIFAR-10 constants its class body assigns first (:122-123, bound into the pipelines before :139-140)
+IMAGENET_R_MEAN, IMAGENET_R_STD = [0.4914, 0.4822, 0.4465], [0.2023, 0.1994, 0.2010]
+TINY_IMAGENET_MEAN, TINY_IMAGENET_STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+
+
+def imagenet_resnet_transform(mode, size, resize, mean, std):
+    common = [ToTensor(), Normalize(mean, std)]
+    if mode == "train":
+        return Compose([RandomResizedCrop(size), RandomHorizontalFlip(), ColorJitter(brightness=63 / 255), *common])
+    return Compose([Resize(resize), CenterCrop(size), *common])
+
+
+def default_transform(config, mode):
+    """the pipeline of a config without `{mode}_trfms`: imagenet-r -> RandomResizedCrop(224) / Resize(256) + CenterCrop(224), tiny-imagenet -> the
+    64 x 64 equivalents (data.py:121-137, 191-211); every other dataset (cifar*, synthetic, ...) keeps cifar_resnet_transform, and so does any ViT"""
+    ds = config.get("dataset", "")
+    bb = config.get("backbone", {})
+    vit = isinstance(bb, dict) and "vit" in str(bb.get("name", "")).lower()
+    if not vit and "cifar" not in ds:
+        if ds == "imagenet-r":
+            return imagenet_resnet_transform(mode, 224, 256, IMAGENET_R_MEAN, IMAGENET_R_STD)
+        if ds == "tiny-imagenet":
+            return imagenet_resnet_transform(mode, 64, 64, TINY_IMAGENET_MEAN, TINY_IMAGENET_STD)
+    return cifar_resnet_transform(mode, config.get("image_size", 32))
+
+
 _BY_NAME.update(RandomCrop=RandomCrop, RandomHorizontalFlip=RandomHorizontalFlip, ColorJitter=ColorJitter, ToTensor=ToTensor, Normalize=Normalize,
                 Resize=Resize, CenterCrop=CenterCrop, RandomResizedCrop=RandomResizedCrop)

@@ -1,6 +1,6 @@
 """ResNet backbones executed as ONE HIP plan per direction (libclhip `clhip_plan_*`).
 
-Drop-in for the reference factories `cifar_resnet20/32`, `resnet18/34` (CIFAR stem), `resnet32_V2`
+Drop-in for the reference factories `cifar_resnet20/32`, `resnet18/34` (CIFAR and ImageNet stems), `resnet32_V2`
 (core/model/backbone/resnet.py:755-778): same constructor kwargs, same `named_parameters()` /
 `named_buffers()` names and shapes (so reference state_dicts load unchanged, and EWC's Fisher / ref
 dicts keep their keys), same return contract `{'features': [B, D], 'fmaps': [...]}` and `feature(x)`.
@@ -49,7 +49,7 @@ class _U:
         self.stride, self.pad, self.src, self.res, self.relu, self.flags = stride, pad, src, res, relu, flags
 
 
-_PRE_RES, _RAW_SRC, _NO_BN = 2, 4, 8        # include/clhip.h: CLHIP_UNIT_*
+_PRE_RES, _RAW_SRC, _NO_BN, _MAXPOOL = 2, 4, 8, 16        # include/clhip.h: CLHIP_UNIT_*
 
 
 def _preact_topology(depth):
@@ -95,7 +95,7 @@ def _stage(units, prefix, blocks, cin, cout, stride, src, names, no_last_relu=Fa
     return src
 
 
-def _topology(kind, depth=None, layers=None):
+def _topology(kind, depth=None, layers=None, stem=None):
     units = []
     if kind == "cifar":            # CifarResNet: resnet.py:324-395
         n = (depth - 2) // 6
@@ -114,8 +114,13 @@ def _topology(kind, depth=None, layers=None):
         s = _stage(units, "layer2", layers[1], 16, 32, 2, s, nm)
         s = _stage(units, "layer3", layers[2], 32, 64, 2, s, nm, no_last_relu=True)
         return units, 64, [], [("layer1", layers[0]), ("layer2", layers[1]), ("layer3", layers[2])]
-    if kind == "imagenet_style":   # ResNet with the CIFAR stem: resnet.py:110-223
-        units.append(_U("conv1.0", "conv1.1", 3, 64, 3, 1, 1, 0, -1, True))
+    if kind == "imagenet_style":   # ResNet: resnet.py:110-223
+        if stem == "imagenet7":    # Conv2d(3, 64, 7, 2, 3) -> BN -> ReLU -> MaxPool2d(3, 2, 1): resnet.py:137-143
+            units.append(_U("conv1.0", "conv1.1", 3, 64, 7, 2, 3, 0, -1, True, _MAXPOOL))
+        elif stem == "imagenet3":  # Conv2d(3, 64, 3, 1, 1) -> BN -> ReLU -> MaxPool2d(3, 2, 1): resnet.py:144-149
+            units.append(_U("conv1.0", "conv1.1", 3, 64, 3, 1, 1, 0, -1, True, _MAXPOOL))
+        else:                      # the CIFAR stem, conv3x3 s1 without max-pool: resnet.py:133-135
+            units.append(_U("conv1.0", "conv1.1", 3, 64, 3, 1, 1, 0, -1, True))
         nm = ("conv1", "bn1", "conv2", "bn2")
         s = _stage(units, "layer1", layers[0], 64, 64, 1, 1, nm)
         s = _stage(units, "layer2", layers[1], 64, 128, 2, s, nm)
@@ -218,10 +223,11 @@ _LIVE = weakref.WeakSet()        # every HipResNet of the process (ops.TeacherPa
 
 
 class HipResNet(nn.Module):
-    def __init__(self, kind, depth=None, layers=None, dtype=None, init="normal_fan_out"):
+    def __init__(self, kind, depth=None, layers=None, dtype=None, init="normal_fan_out", stem=None):
         super().__init__()
         _LIVE.add(self)
-        self._units, self.out_dim, extra, self._stages = _topology(kind, depth, layers)
+        self.stem = stem or "cifar"
+        self._units, self.out_dim, extra, self._stages = _topology(kind, depth, layers, stem)
         self.feat_dim = self.out_dim
         self._dtype = _dtype_code(dtype)
         # ---- flat parameter layout (forward order; the unused `fc` stays outside the flat range so
@@ -586,7 +592,10 @@ class HipResNet(nn.Module):
         dims = {0: (H, W)}
         for i, u in enumerate(self._units):
             hs, ws_ = dims[u.src]
-            dims[i + 1] = ((hs + 2 * u.pad - u.k) // u.stride + 1, (ws_ + 2 * u.pad - u.k) // u.stride + 1)
+            ho, wo = (hs + 2 * u.pad - u.k) // u.stride + 1, (ws_ + 2 * u.pad - u.k) // u.stride + 1
+            if u.flags & _MAXPOOL:                     # MaxPool2d(3, stride 2, pad 1)
+                ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+            dims[i + 1] = (ho, wo)
         return dims
 
     def _read_act(self, state, act, which, channels):
@@ -656,19 +665,28 @@ def resnet32_V2(pretrained=False, **kwargs):
     return HipResNet("modified", layers=[5, 5, 5], dtype=kwargs.get("dtype"))
 
 
-def _imagenet_style(layers, kwargs):
-    args = kwargs.get("args")
+def stem_for(args):
+    """the stem the reference's ResNet.__init__ builds for `args` (resnet.py:132-149): 'cifar' (conv3x3 s1, no max-pool) when the dataset
+    name contains 'cifar' or '5-datasets', else 'imagenet7' (conv7x7 s2 + max-pool) / 'imagenet3' (conv3x3 s1 + max-pool) when it contains
+    'imagenet', by whether the first task has as many classes as the later ones"""
     assert args is not None, "you should pass args to resnet"          # resnet.py:132
     ds = args["dataset"]
-    if not ("cifar" in ds or "5-datasets" in ds):
-        raise NotImplementedError("only the CIFAR stem (conv3x3 s1, no max-pool; resnet.py:133-135) is on the hot path")
+    if "cifar" in ds or "5-datasets" in ds:
+        return "cifar"
+    if "imagenet" in ds:
+        return "imagenet7" if args["init_cls_num"] == args["inc_cls_num"] else "imagenet3"
+    raise NotImplementedError(f"dataset {ds!r}: the reference ResNet builds no stem for it (resnet.py:133-149)")
+
+
+def _imagenet_style(layers, kwargs):
+    stem = stem_for(kwargs.get("args"))
     if kwargs.get("pretrained"):
         raise NotImplementedError
-    return HipResNet("imagenet_style", layers=layers, dtype=kwargs.get("dtype"))
+    return HipResNet("imagenet_style", layers=layers, dtype=kwargs.get("dtype"), stem=stem)
 
 
 def resnet18(pretrained=False, progress=True, **kwargs):
-    """reference factory resnet.py:259-267 (LwF backbone with args.dataset containing 'cifar')"""
+    """reference factory resnet.py:259-267 (CIFAR stem for 'cifar' / '5-datasets', ImageNet stem with max-pool for 'imagenet' datasets)"""
     return _imagenet_style([2, 2, 2, 2], dict(kwargs, pretrained=pretrained))
 
 
