@@ -656,6 +656,25 @@ int clhip_augment_rrc_aa(const uint8_t* store, const int64_t* offsets /*nullable
                          const int32_t* params, float* out, void* ws, int B, int H, int W, int S, int max_box, const float* mean3,
                          const float* std3, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RanPAC: random-projection ridge classifier (core/model/ranpac.py) in exact fp32 on the f32-input MFMA (csrc/rp.hip).  Everything is fp32,
+ * row-major and dense; no atomics, fixed summation order (bitwise reproducible); any N, D, M, C, B >= 1.
+ * project   : H [N, M] = F [N, D] W [D, M], through a ReLU when relu != 0  (ranpac.py:248 and :55; W_rand as :221 stores it)
+ * gram_accum: G [M, M] += H^T H  (ranpac.py:251, :257).  Only the tiles on or above the diagonal are computed and each is written to both places:
+ *             G stays exactly symmetric.  No split along N; successive calls accumulate (read-modify-write of the tile).
+ * label_sum : Q [M, C] += H^T onehot(labels), a per-class column sum with the rows in ascending order (ranpac.py:246, :250, :256); labels: int64
+ *             [N] on the device.  A label outside [0, C) makes the call return CLHIP_EINVAL before Q is touched (checked on the device copy; this
+ *             call synchronises the stream).
+ * classify  : logits [B, C] = sigma * relu(X [B, D] W [D, M]) Wo [C, M]^T, the use_RP branch of CosineLinear.forward (ranpac.py:53-61).  sigma: one
+ *             float on the device (NULL: 1).  ws: clhip_rp_classify_ws_bytes(B, M, C) bytes (the hidden rows and the K-slice partials, which are
+ *             summed in slice order). */
+int clhip_rp_project(const float* F, const float* W, float* H, int N, int D, int M, int relu, void* stream);
+int clhip_rp_gram_accum(const float* H, float* G, int N, int M, void* stream);
+int clhip_rp_label_sum(const float* H, const int64_t* labels, float* Q, int N, int M, int C, void* stream);
+size_t clhip_rp_classify_ws_bytes(int B, int M, int C);
+int clhip_rp_classify(const float* X, const float* W, const float* Wo, const float* sigma /*nullable*/, float* logits, void* ws, int B, int D, int M,
+                      int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,11 @@ _PROTOS = {
     "clhip_vit_forward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _i, _p, _i, _i, _p, _p, _p]),
     "clhip_vit_backward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p]),
     "clhip_vit_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
+    "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
+    "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "clhip_rp_classify_ws_bytes": (_sz, [_i, _i, _i]),
+    "clhip_rp_classify": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _CHECKED = {}

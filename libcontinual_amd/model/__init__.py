@@ -13,4 +13,5 @@ from .bic import bic, BiasLayer  # noqa: F401
 from .l2p import L2P  # noqa: F401
 from .inflora_opt import InfLoRA_OPT  # noqa: F401
 from .inflora import InfLoRA  # noqa: F401
+from .ranpac import RanPAC, RPClassifier  # noqa: F401
 from .heads import HipLinear  # noqa: F401

@@ -556,3 +556,11 @@ class ViTZoo(nn.Module):
 
 def vit_pt_imnet(pretrained=False, **kwargs):
     return ViTZoo(pretrained, **kwargs)
+
+
+def vit_pt_imnet_in21k_adapter(pretrained=False, **kwargs):
+    """the backbone name of the reference's RanPAC config (config/ranpac.yaml:48-52; core/model/backbone/vit.py ViT_in21k_adapter).  Its AdaptFormer
+    adapters start as the identity (`up_proj` is zero-initialised, petl/adapter.py:45-50) and only first-session training moves them, which
+    model/ranpac.py does not implement: the frozen network is the plain ViT-B/16 with the ImageNet-21k weights."""
+    kwargs.setdefault("model_name", "vit_base_patch16_224_in21k")
+    return ViTZoo(pretrained, **kwargs)

@@ -388,6 +388,60 @@ def ncm_classify(feats, means):
     return pred
 
 
+
+# ------------------------------------------------------------------------------------------ RanPAC (csrc/rp.hip: exact fp32 on the f32-input MFMA)
+def rp_project(feats, w_rand, relu=True):
+    """relu(feats [N, D] @ w_rand [D, M]) (ranpac.py:248, :55)"""
+    feats, w_rand = _f32c(feats), _f32c(w_rand)
+    _dev(feats, w_rand)
+    (N, D), M = feats.shape, w_rand.shape[1]
+    assert w_rand.shape[0] == D
+    out = torch.empty(N, M, device=feats.device, dtype=torch.float32)
+    call("clhip_rp_project", _ptr(feats), _ptr(w_rand), _ptr(out), N, D, M, int(bool(relu)), _st())
+    return out
+
+
+def _rp_state(t, shape):
+    require_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.ClhipError(f"accumulator must be a contiguous fp32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def rp_gram_accum(H, G):
+    """G [M, M] += H^T H in place, exactly symmetric (ranpac.py:251, :257)"""
+    H = _f32c(H)
+    _dev(H, G)
+    N, M = H.shape
+    _rp_state(G, (M, M))
+    call("clhip_rp_gram_accum", _ptr(H), _ptr(G), N, M, _st())
+    return G
+
+
+def rp_label_sum(H, labels, Q):
+    """Q [M, C] += H^T onehot(labels) in place (ranpac.py:250, :256); a label outside [0, C) raises"""
+    H = _f32c(H)
+    _dev(H, labels, Q)
+    N, M = H.shape
+    _rp_state(Q, (M, Q.shape[1]))
+    labels = labels.to(torch.int64).contiguous()
+    assert labels.numel() == N
+    call("clhip_rp_label_sum", _ptr(H), _ptr(labels), _ptr(Q), N, M, Q.shape[1], _st())
+    return Q
+
+
+def rp_classify(x, w_rand, wo, sigma=None):
+    """sigma * relu(x [B, D] @ w_rand [D, M]) @ wo [C, M]^T: the use_RP branch of CosineLinear.forward (ranpac.py:53-61)"""
+    x, w_rand, wo = _f32c(x), _f32c(w_rand), _f32c(wo)
+    sigma = _f32c(sigma) if sigma is not None else None
+    _dev(x, w_rand, wo, sigma)
+    (B, D), M, C = x.shape, w_rand.shape[1], wo.shape[0]
+    assert w_rand.shape[0] == D and wo.shape[1] == M
+    ws = torch.empty(_lib.lib().clhip_rp_classify_ws_bytes(B, M, C), device=x.device, dtype=torch.uint8)
+    out = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    call("clhip_rp_classify", _ptr(x), _ptr(w_rand), _ptr(wo), _ptr(sigma), _ptr(out), _ptr(ws), B, D, M, C, _st())
+    return out
+
+
 def herding_select(feats_normed, m):
     """indices (int32 tensor [min(m,n)]) chosen by the greedy mean-matching of linearherdingbuffer.py:140-161."""
     f = _f32c(feats_normed)
