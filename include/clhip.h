@@ -600,16 +600,39 @@ int clhip_l2p_select(const float* cls_feat, const float* prompt_key, const float
                      int* ids, float* prompt_tokens, float* reduce_sim, float* dkey, float* scratch, void* stream);
 int clhip_l2p_scatter(const float* dtokens, const int* ids, float* dprompt_pool, int pool, int top_k, int length, int D, void* stream);
 
+/* AdaptFormer adapter branch (csrc/adapter.hip; petl/vision_transformer_adapter.py:31-90): x, y, hd, dh, gy, gx in the compute dtype, the
+ * weights fp32 masters (down_w [R, D], down_b [R], up_w [D, R], up_b [D]); R in {16, 32, 64}, D % 64 == 0, 0 <= p < 1, any M >= 1.  No atomics,
+ * bitwise reproducible.
+ * fwd  : y [M, D] += scale * (drop(relu(x down_w^T + down_b)) up_w^T + up_b) in one launch; hd (nullable) [M, R] = the dropped hidden rows.
+ *        Dropout keeps element (row, col) iff a hash of (*seed, layer, row, col) says so and scales it by 1 / (1 - p); seed: one 64-bit word in
+ *        device memory, required iff p > 0.  p == 0: nothing is drawn or scaled.
+ *        0 < p < 2^-24 is refused (24 hash bits).  fwd / bwd: a workgroup owns 32 or 64 rows; clhip_config("ADAPTER_TM", "32" | "64") pins it.
+ * bwd  : dh [M, R] = ((scale * gy) up_w) * [hd > 0] / (1 - p);  gx [M, D] = gy + dh down_w  (gx may be gy)
+ * wgrad: d_up_w = scale * gy^T hd, d_up_b = scale * sum_rows gy, d_down_w = dh^T x, d_down_b = sum_rows dh (written, not accumulated);
+ *        ws: clhip_adapter_wgrad_ws_bytes(M, D, R) bytes (row-slab partials, reduced in slab order)
+ * dropout_mask: out [M, R] bytes, 1 = kept -- the mask clhip_adapter_fwd applies for the same (seed, layer, p) */
+int clhip_adapter_fwd(const void* x, const float* down_w, const float* down_b, const float* up_w, const float* up_b, void* y, void* hd,
+                      const unsigned long long* seed, int layer, float p, float scale, int M, int D, int R, int dtype, void* stream);
+int clhip_adapter_bwd(const void* gy, const void* hd, const float* up_w, const float* down_w, void* dh, void* gx, float p, float scale, int M,
+                      int D, int R, int dtype, void* stream);
+size_t clhip_adapter_wgrad_ws_bytes(int M, int D, int R);
+int clhip_adapter_wgrad(const void* gy, const void* hd, const void* x, const void* dh, float* d_up_w, float* d_up_b, float* d_down_w,
+                        float* d_down_b, void* ws, float scale, int M, int D, int R, int dtype, void* stream);
+int clhip_adapter_dropout_mask(const unsigned long long* seed, int layer, int M, int R, float p, unsigned char* out, void* stream);
+
 /* Whole-backbone executor: one C call per forward / backward (VisionTransformer.forward, transformer.py:2222-2294, and
  * the autograd backward of L2P.observe / the trainer's loss.backward()). */
 typedef struct clhip_vit_desc {
     int32_t img, patch, dim, depth, heads, mlp, lora_rank;
     float block_ln_eps;   /* eps of the per-block LayerNorms: 0 -> 1e-5 (transformer.py nn.LayerNorm default); timm-style trees
                            * (vit_inflora.py:375) use 1e-6 everywhere.  The final norm is 1e-6 in both. */
+    int32_t adapter_dim;  /* AdaptFormer bottleneck width R in {16, 32, 64}; 0: no adapters (the executor is then exactly what it was) */
+    float adapter_scale;  /* s of x_out = x_mid + mlp(LN2(x_mid)) + s * adapter(x_mid) */
 } clhip_vit_desc;
 typedef struct clhip_vit_layer_params {
     const float *qkv_w, *qkv_b, *proj_w, *proj_b, *ln1_w, *ln1_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ln2_w, *ln2_b;
     const float *lora_a_k, *lora_b_k, *lora_a_v, *lora_b_v;          /* NULL without LoRA */
+    const float *ad_down_w, *ad_down_b, *ad_up_w, *ad_up_b;          /* adapter [R, D], [R], [D, R], [D]; NULL without adapters */
 } clhip_vit_layer_params;
 typedef struct clhip_vit_params {
     const float *cls_token, *pos_embed, *pe_w, *pe_b, *norm_w, *norm_b;
@@ -631,6 +654,14 @@ int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const void* shado
  * (k, v per layer) accumulated into */
 int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                        float* dprompt_tokens, float* const* d_lora_b, void* stream);
+/* adapter dropout of the NEXT clhip_vit_forward (and of the backward that follows it): probability p in [0, 1) and the 64-bit seed in device
+ * memory (required iff p > 0; read when the kernels run, so it must stay alive until then).  The forward consumes the state: forwards after it
+ * run without dropout until this is called again. */
+int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long long* seed, float p);
+/* clhip_vit_backward that also FILLS the adapter gradients: d_adapter = [4*depth] pointers (d down_w [R, D], d down_b [R], d up_w [D, R],
+ * d up_b [D] per layer), nullable.  With adapters the input gradient of every adapter branch is part of the chain either way. */
+int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
+                               float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream);
 /* debug/test: copy one saved activation of layer l (0 x_in, 1 qkv, 2 attn out, 3 x_mid, 4 GELU derivative of the mlp) to fp32 */
 int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream);
 

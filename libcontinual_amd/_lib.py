@@ -27,12 +27,14 @@ class UnitDesc(C.Structure):
 
 
 class VitDesc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("img", "patch", "dim", "depth", "heads", "mlp", "lora_rank")] + [("block_ln_eps", C.c_float)]
+    _fields_ = [(n, C.c_int32) for n in ("img", "patch", "dim", "depth", "heads", "mlp", "lora_rank")] + [("block_ln_eps", C.c_float),
+                                                                                                                   ("adapter_dim", C.c_int32), ("adapter_scale", C.c_float)]
 
 
 class VitLayerParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "qkv_b", "proj_w", "proj_b", "ln1_w", "ln1_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b",
-                                          "ln2_w", "ln2_b", "lora_a_k", "lora_b_k", "lora_a_v", "lora_b_v")]
+                                          "ln2_w", "ln2_b", "lora_a_k", "lora_b_k", "lora_a_v", "lora_b_v",
+                                          "ad_down_w", "ad_down_b", "ad_up_w", "ad_up_b")]
 
 
 class VitParams(C.Structure):
@@ -191,6 +193,13 @@ _PROTOS = {
     "clhip_vit_forward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _i, _p, _i, _i, _p, _p, _p]),
     "clhip_vit_backward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p]),
     "clhip_vit_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
+    "clhip_vit_set_adapter_dropout": (_i, [_p, _p, _f]),
+    "clhip_vit_backward_adapter": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _p]),
+    "clhip_adapter_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _i, _i, _i, _i, _p]),
+    "clhip_adapter_bwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
+    "clhip_adapter_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
+    "clhip_adapter_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _p]),
+    "clhip_adapter_dropout_mask": (_i, [_p, _i, _i, _i, _f, _p, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -1,7 +1,8 @@
 // vit_plan.hip -- whole-backbone executor for the ViT path: one C call runs the complete forward (patch embedding,
 // token assembly with optional L2P prompt tokens, depth x [LN -> qkv -> attention -> proj(+res) -> LN -> fc1(GELU)
 // -> fc2(+res)], final LN + pooling) or the complete activation-gradient backward (every weight of the backbone is
-// frozen in L2P and InfLoRA_OPT; the only parameter gradients are the prompt tokens and the LoRA B matrices).
+// frozen in L2P and InfLoRA_OPT; the only parameter gradients are the prompt tokens, the LoRA B matrices and, with adapter_dim > 0, the
+// AdaptFormer adapters of csrc/adapter.hip -- RanPAC's first session).
 // Replaces VisionTransformer.forward / Transformer.forward / ResidualAttentionBlock.forward
 // (core/model/backbone/transformer.py:2222-2294, 2006-2018, 1331-1336) and the autograd graph behind
 // loss.backward() (l2p.py:103, trainer.py:604).  Nothing here allocates or synchronises: fixed workspace offsets.
@@ -19,8 +20,8 @@ struct LayerShadow { size_t qkv_f, qkv_b, proj_f, proj_b, fc1_f, fc1_b, fc2_f, f
 
 struct Layout {          // byte offsets into the workspace for one (B, n_prompt, save) configuration
     int B, P, N, M, save;
-    size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, total;
-    std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse;   // per layer (x_in has depth+1 entries)
+    size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, g2, ad_dh, ad_ws, total;
+    std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse, ad_hd;   // per layer (x_in has depth+1 entries)
 };
 
 template <typename T>
@@ -38,6 +39,9 @@ struct clhip_vit {
     bool have_last;
     hipStream_t side;     // stream of the LoRA weight gradients (leaves of the backward chain), created on first use
     hipEvent_t ev_q, ev_l;
+    const unsigned long long* drop_seed;   // adapter dropout of the next forward (clhip_vit_set_adapter_dropout) ...
+    float drop_p;
+    float last_p;                          // ... and of the forward the backward belongs to
 };
 
 // `flags`: bit 0 = keep what the backward needs; bit 1 (CLHIP_VIT_KEEP_ATTN_IN) = keep every layer's attention input (LN1 output) until the
@@ -92,14 +96,25 @@ static void make_layout(const clhip_vit* v, int B, int P, int flags, Layout& L) 
     } else {
         L.g = L.dtmp = L.dbig = L.dqkv = L.dsum = L.lora_ws = 0;
     }
+    // adapters (appended: without them every offset above and the total are what they were): the dropped hidden rows of every layer, dh, the
+    // second gradient buffer (the adapter's input gradient is written out of place, so its weight gradient still reads dL/dx_out) and the slabs
+    L.ad_hd.assign(d.depth, 0);
+    L.g2 = L.ad_dh = L.ad_ws = 0;
+    if (save && d.adapter_dim > 0) {
+        for (int l = 0; l < d.depth; ++l) L.ad_hd[l] = take(M * d.adapter_dim * e);
+        L.ad_dh = take(M * d.adapter_dim * e);
+        L.g2 = take(M * D * e);
+        L.ad_ws = take(clhip_adapter_wgrad_ws_bytes(L.M, d.dim, d.adapter_dim));
+    }
     L.total = off;
 }
 
 extern "C" clhip_vit* clhip_vit_create(const clhip_vit_desc* desc, int dtype) {
     if (!desc || (dtype != CLHIP_BF16 && dtype != CLHIP_F32) || desc->dim <= 0 || desc->depth <= 0 || desc->heads <= 0 || desc->dim % desc->heads ||
         desc->patch <= 0 || desc->img % desc->patch || desc->dim % 64 || desc->mlp % 64 || (3 * desc->patch * desc->patch) % 64 ||
-        desc->dim / desc->heads > 64 || desc->lora_rank < 0 || desc->lora_rank > 16) {
-        clhip_set_error("clhip_vit_create: invalid descriptor (dim, mlp and 3*patch^2 must be multiples of 64; head dim <= 64; rank <= 16)");
+        desc->dim / desc->heads > 64 || desc->lora_rank < 0 || desc->lora_rank > 16 ||
+        (desc->adapter_dim != 0 && desc->adapter_dim != 16 && desc->adapter_dim != 32 && desc->adapter_dim != 64)) {
+        clhip_set_error("clhip_vit_create: invalid descriptor (dim, mlp and 3*patch^2 must be multiples of 64; head dim <= 64; rank <= 16; adapter_dim 0, 16, 32 or 64)");
         return nullptr;
     }
     clhip_vit* v = new (std::nothrow) clhip_vit();
@@ -122,6 +137,7 @@ extern "C" clhip_vit* clhip_vit_create(const clhip_vit_desc* desc, int dtype) {
     }
     v->shadow_bytes = off;
     v->have_last = false;
+    v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = 0.f;
     return v;
 }
 
@@ -142,6 +158,14 @@ extern "C" size_t clhip_vit_workspace_bytes(const clhip_vit* v, int B, int n_pro
 }
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != CLHIP_OK) return rc_; } while (0)
+
+extern "C" int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long long* seed, float p) {
+    CLHIP_CHECK_ARG(v && v->d.adapter_dim > 0);
+    CLHIP_CHECK_ARG(p == 0.f || (p < 1.f && p * 16777216.f >= 1.f));     // the kernels' rule: 24 hash bits cannot tell a smaller p from 0
+    CLHIP_CHECK_ARG((p > 0.f) == (seed != nullptr));
+    v->drop_seed = seed; v->drop_p = p;
+    return CLHIP_OK;
+}
 
 extern "C" int clhip_vit_prep_weights(clhip_vit* v, const clhip_vit_params* P, void* shadow, int apply_lora, int qkv_only, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow);
@@ -189,6 +213,10 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
     const char* sh = static_cast<const char*>(shadow);
     const int D = d.dim, Hm = d.mlp, M = L.M, N = L.N, dt = v->dtype;
     const float beps = d.block_ln_eps > 0.f ? d.block_ln_eps : 1e-5f;
+    const int R = d.adapter_dim;
+    const unsigned long long* drop_seed = v->drop_seed;
+    const float drop_p = v->drop_p;
+    v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = drop_p;             // the dropout state is consumed by this forward
     // patch embedding (timm PatchEmbed = Conv2d(3, D, p, stride p)) as patchify + GEMM, then token assembly
     TRY(clhip_patchify(images, ws + L.patches, B, d.img, d.patch, dt, stream));
     TRY(clhip_gemm_nt(ws + L.patches, sh + v->pe_f, ws + L.pe_out, P->pe_b, nullptr, nullptr, B * v->np, D, v->Kp, v->Kp, v->Kp, D, 0, 0, EPI_BIAS, dt, stream));
@@ -207,6 +235,11 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
         TRY(clhip_gemm_nt(ws + L.ln_out, sh + s.fc1_f, ws + L.act, p.fc1_b, nullptr, save ? ws + L.hpre[l] : nullptr, M, Hm, D, D, D, Hm, 0, Hm, EPI_BIAS_GELU, dt,
                           stream));
         TRY(clhip_gemm_nt(ws + L.act, sh + s.fc2_f, ws + L.x_in[l + 1], p.fc2_b, ws + L.x_mid[l], nullptr, M, D, Hm, Hm, Hm, D, D, 0, EPI_BIAS_RES, dt, stream));
+        if (R > 0) {                                         // x_out += s * adapter(x_mid), parallel to the MLP (vision_transformer_adapter.py:165-183)
+            CLHIP_CHECK_ARG(p.ad_down_w && p.ad_down_b && p.ad_up_w && p.ad_up_b);
+            TRY(clhip_adapter_fwd(ws + L.x_mid[l], p.ad_down_w, p.ad_down_b, p.ad_up_w, p.ad_up_b, ws + L.x_in[l + 1], save ? ws + L.ad_hd[l] : nullptr,
+                                  drop_seed, l, drop_p, d.adapter_scale, M, D, R, dt, stream));
+        }
     }
     if (gram) {
         // every layer's attention input is still there (make_layout bit 1, or the backward's own copies): X_l^T X_l of all layers, one launch
@@ -220,7 +253,13 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
 
 extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
                                   float* const* d_lora_b, void* stream) {
+    return clhip_vit_backward_adapter(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, stream);
+}
+
+extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
+                                          float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && dfeat);
+    CLHIP_CHECK_ARG(d_adapter == nullptr || v->d.adapter_dim > 0);
     CLHIP_CHECK_ARG(v->have_last && v->last.save);
     const clhip_vit_desc& d = v->d;
     const Layout& L = v->last;
@@ -230,6 +269,8 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
     const char* sh = static_cast<const char*>(shadow);
     const int D = d.dim, Hm = d.mlp, M = L.M, N = L.N, B = L.B, dt = v->dtype;
     char* g = ws + L.g;
+    char* g2 = ws + L.g2;
+    const int R = d.adapter_dim;
     // the lora_B gradients are leaves of the chain: they run on a side stream (ordered by events against the single dqkv buffer)
     static const bool two_streams = !(clhip_cfg("WGRAD_STREAM") && atoi(clhip_cfg("WGRAD_STREAM")) == 0);
     hipStream_t main_s = static_cast<hipStream_t>(stream);
@@ -254,6 +295,19 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
         const float* st2 = reinterpret_cast<const float*>(ws + L.st2[l]);
         // MLP branch: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
         TRY(clhip_gemm_nt(g, sh + s.fc2_b, ws + L.dbig, nullptr, nullptr, ws + L.hpre[l], M, Hm, D, D, D, Hm, 0, Hm, EPI_MUL, dt, stream));
+        if (R > 0) {
+            // adapter branch: g is dL/dx_out here (the fc2 dgrad above has read it, LN2's += comes below).  g2 = g + dh Wd, then the two buffers
+            // swap roles: the chain goes on in g2 and the weight gradient still finds dL/dx_out in the old one.  One stream: one summation order.
+            CLHIP_CHECK_ARG(p.ad_down_w && p.ad_up_w);
+            TRY(clhip_adapter_bwd(g, ws + L.ad_hd[l], p.ad_up_w, p.ad_down_w, ws + L.ad_dh, g2, v->last_p, d.adapter_scale, M, D, R, dt, stream));
+            if (d_adapter) {
+                float* const* ga = d_adapter + 4 * l;
+                CLHIP_CHECK_ARG(ga[0] && ga[1] && ga[2] && ga[3]);
+                TRY(clhip_adapter_wgrad(g, ws + L.ad_hd[l], ws + L.x_mid[l], ws + L.ad_dh, ga[2], ga[3], ga[0], ga[1], ws + L.ad_ws, d.adapter_scale, M, D, R,
+                                        dt, stream));
+            }
+            char* t = g; g = g2; g2 = t;
+        }
         TRY(clhip_gemm_nt(ws + L.dbig, sh + s.fc1_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, Hm, Hm, Hm, D, 0, 0, EPI_NONE, dt, stream));
         TRY(clhip_ln_bwd(ws + L.dtmp, ws + L.x_mid[l], p.ln2_w, st2, st2 + M, g, M, D, dt, stream));
         // attention branch: x_mid = x_in + proj(attn(qkv(LN1(x_in))))

@@ -6,6 +6,7 @@ kwargs and plugin code written against it keep working:
     ViTZoo                     core/model/backbone/vit.py:43-139     (.feat, .prompt, .prompt_flag, create_prompt, forward)
       feat: VisionTransformer  core/model/backbone/transformer.py:2147-2294
         patch_embed.proj, cls_token, pos_embed, transformer.blocks[i].{ln_1, attn.{qkv, proj[, lora_*]}, ln_2, mlp.{fc1, fc2}}, norm
+        [ffn_adapt: transformer.blocks[i].adaptmlp.{down_proj, up_proj}   core/model/backbone/petl/vision_transformer_adapter.py:31-90]
     MultiHeadAttention_LoRA    transformer.py:199-274   (apply_lora, init_param, merge_weight, reset_input_matrix, cur_matrix)
     L2PPrompt                  core/model/backbone/prompt.py:345-406 (prompt, prompt_key)
 
@@ -153,6 +154,27 @@ class Mlp(nn.Module):
         self.fc1, self.fc2 = _P((hidden, dim)), _P((dim, hidden))
 
 
+class Adapter(nn.Module):
+    """petl/vision_transformer_adapter.py:31-90 with ffn_adapter_layernorm_option "none": down_proj [R, D] -> ReLU -> dropout -> up_proj [D, R], times
+    `scale`, added to the block output in parallel to the MLP.  init_option "lora": kaiming_uniform(a = sqrt 5) on down_proj, zeros elsewhere, so a
+    fresh adapter is the identity."""
+
+    def __init__(self, dim, bottleneck, scale=0.1, dropout=0.1):
+        super().__init__()
+        self.n_embd, self.down_size, self.scale, self.dropout = dim, bottleneck, float(scale), float(dropout)
+        self.down_proj, self.up_proj = _P((bottleneck, dim)), _P((dim, bottleneck))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.down_proj.weight, a=math.sqrt(5))
+        nn.init.zeros_(self.up_proj.weight)
+        nn.init.zeros_(self.down_proj.bias)
+        nn.init.zeros_(self.up_proj.bias)
+
+    def tensors(self):
+        return [self.down_proj.weight, self.down_proj.bias, self.up_proj.weight, self.up_proj.bias]
+
+
 class ResidualAttentionBlock(nn.Module):
     def __init__(self, dim, heads, mlp_ratio, attn_layer, **kw):
         super().__init__()
@@ -196,14 +218,15 @@ class _Scratch:
 
 
 class _VitFn(torch.autograd.Function):
-    """features = ViT(images [, prompt tokens]); backward -> d prompt tokens and / or d lora_B of every layer"""
+    """features = ViT(images [, prompt tokens]); backward -> d prompt tokens and / or d lora_B and / or the four adapter gradients of every
+    layer.  `params` = the n_lora lora_B weights, then the adapter tensors (down w, down b, up w, up b per layer)"""
 
     @staticmethod
-    def forward(ctx, vit, images, prompt_tokens, gram, need, *lora_b):
+    def forward(ctx, vit, images, prompt_tokens, gram, need, n_lora, *params):
         feat = vit._run_forward(images, prompt_tokens, need, gram)
-        ctx.vit, ctx.n_lora, ctx.has_prompt = vit, len(lora_b), prompt_tokens is not None
+        ctx.vit, ctx.n_lora, ctx.has_prompt = vit, n_lora, prompt_tokens is not None
+        ctx.n_adapter = len(params) - n_lora
         ctx.token = vit._fwd_token
-        ctx.lora_shapes = [tuple(b.shape) for b in lora_b]
         return feat
 
     @staticmethod
@@ -211,13 +234,13 @@ class _VitFn(torch.autograd.Function):
         vit = ctx.vit
         if vit._fwd_token != ctx.token:
             raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
-        dprompt, dlora = vit._run_backward(dfeat, ctx.has_prompt, ctx.n_lora > 0)
-        return (None, None, dprompt, None, None) + tuple(dlora if dlora else ())
+        dprompt, dlora, dad = vit._run_backward(dfeat, ctx.has_prompt, ctx.n_lora > 0, ctx.n_adapter > 0)
+        return (None, None, dprompt, None, None, None) + tuple(dlora if dlora else ()) + tuple(dad if dad else ())
 
 
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, attn_layer="MultiHeadAttention",
-                 mlp_ratio=4.0, dtype="bf16", lora_rank=0, **kwargs):
+                 mlp_ratio=4.0, dtype="bf16", lora_rank=0, ffn_adapt=False, ffn_num=64, ffn_adapter_scalar=0.1, adapter_dropout=0.1, **kwargs):
         super().__init__()
         assert in_chans == 3
         if isinstance(attn_layer, str):
@@ -238,6 +261,22 @@ class VisionTransformer(nn.Module):
         self._s = _Scratch()
         self._fwd_token = 0
         self.reset_parameters()
+        # AdaptFormer adapters (the reference's tuning config of vit_pt_imnet_in21k_adapter: ffn_adapt, ffn_num 64, scalar 0.1, dropout 0.1): created
+        # after every other parameter, so a model without them draws exactly the initial values it always drew.  The adapter tree is timm's:
+        # every LayerNorm has eps 1e-6, and only the adapters train (vision_transformer_adapter.py:461-466).
+        self.adapter_dim = int(ffn_num) if ffn_adapt else 0
+        self.adapter_scale, self.adapter_dropout = float(ffn_adapter_scalar), float(adapter_dropout)
+        self.last_dropout_seed = None
+        if self.adapter_dim:
+            if self.adapter_dim not in (16, 32, 64):
+                raise NotImplementedError(f"ffn_num {ffn_num}: the adapter kernels take a bottleneck of 16, 32 or 64")
+            if not 0.0 <= self.adapter_dropout < 1.0:
+                raise ValueError(f"adapter_dropout {adapter_dropout} is outside [0, 1)")
+            self.block_ln_eps = 1e-6
+            for p in self.parameters():
+                p.requires_grad_(False)
+            for blk in self.transformer.blocks:
+                blk.adaptmlp = Adapter(embed_dim, self.adapter_dim, self.adapter_scale, self.adapter_dropout)
 
     # ------------------------------------------------------------------ init (transformer.py:2201-2213, timm PatchEmbed)
     def reset_parameters(self):
@@ -262,6 +301,10 @@ class VisionTransformer(nn.Module):
     def attention_modules(self):
         return [b.attn for b in self.transformer.blocks]
 
+    def adapter_tensors(self):
+        """down w, down b, up w, up b of every layer, in layer order (empty without adapters)"""
+        return [t for b in self.transformer.blocks for t in b.adaptmlp.tensors()] if self.adapter_dim else []
+
     def _frozen_tensors(self):
         out = [self.patch_embed.proj.weight]
         for b in self.transformer.blocks:
@@ -275,7 +318,7 @@ class VisionTransformer(nn.Module):
         s = self._s
         if s.handle is None:
             desc = _lib.VitDesc(self.img_size, self.patch_size, self.embed_dim, self.depth, self.num_heads, self.mlp_dim, self.lora_rank,
-                                float(getattr(self, "block_ln_eps", 0.0)))
+                                float(getattr(self, "block_ln_eps", 0.0)), self.adapter_dim, self.adapter_scale)
             h = _lib.lib().clhip_vit_create(C.byref(desc), _DT[self.compute_dtype][0])
             if not h:
                 raise _lib.ClhipError(_lib.lib().clhip_last_error().decode())
@@ -302,6 +345,8 @@ class VisionTransformer(nn.Module):
                 if self.lora_rank:
                     L.lora_a_k, L.lora_b_k = b.attn.lora_A_k.weight.data_ptr(), b.attn.lora_B_k.weight.data_ptr()
                     L.lora_a_v, L.lora_b_v = b.attn.lora_A_v.weight.data_ptr(), b.attn.lora_B_v.weight.data_ptr()
+                if self.adapter_dim:
+                    L.ad_down_w, L.ad_down_b, L.ad_up_w, L.ad_up_b = [t.data_ptr() for t in b.adaptmlp.tensors()]
             cp = _lib.VitParams(self.cls_token.data_ptr(), self.pos_embed.data_ptr(), self.patch_embed.proj.weight.data_ptr(),
                                 self.patch_embed.proj.bias.data_ptr(), self.norm.weight.data_ptr(), self.norm.bias.data_ptr(), layers)
             s.cparams, s.keep, s._layers = cp, ptrs, layers
@@ -348,6 +393,11 @@ class VisionTransformer(nn.Module):
             n_prompt = prompt_tokens.shape[0]
         ws = self._workspace(s, B, n_prompt, int(bool(save)) | (2 if gram is not None else 0), dev)
         feat = torch.empty(B, self.embed_dim, device=dev, dtype=torch.float32)
+        self.last_dropout_seed = None
+        if self.adapter_dim and self.training and self.adapter_dropout > 0.0:
+            # one 64-bit word from the device generator (the one init_seed seeds): no synchronisation, and the CPU generator is left alone
+            self.last_dropout_seed = torch.empty(1, dtype=torch.int64, device=dev).random_()
+            call("clhip_vit_set_adapter_dropout", s.handle, self.last_dropout_seed.data_ptr(), self.adapter_dropout)
         call("clhip_vit_forward", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), ws.data_ptr(), images.data_ptr(), B,
              prompt_tokens.data_ptr() if n_prompt else None, n_prompt, int(save), gram.data_ptr() if gram is not None else None,
              feat.data_ptr(), _st())
@@ -355,7 +405,7 @@ class VisionTransformer(nn.Module):
         self._last = (B, n_prompt)
         return feat
 
-    def _run_backward(self, dfeat, want_prompt, want_lora):
+    def _run_backward(self, dfeat, want_prompt, want_lora, want_adapter=False):
         s = self._s
         B, n_prompt = self._last
         dfeat = dfeat.float().contiguous()
@@ -365,9 +415,19 @@ class VisionTransformer(nn.Module):
         if want_lora:
             dl = list(torch.zeros(2 * self.depth, self.embed_dim, self.lora_rank, device=dev).unbind(0))     # one fill, 2*depth views
             arr = (C.c_void_p * (2 * self.depth))(*[t.data_ptr() for t in dl])
-        call("clhip_vit_backward", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
-             dprompt.data_ptr() if want_prompt else None, arr, _st())
-        return dprompt, dl
+        if not want_adapter:
+            call("clhip_vit_backward", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
+                 dprompt.data_ptr() if want_prompt else None, arr, _st())
+            return dprompt, dl, None
+        D, R = self.embed_dim, self.adapter_dim
+        flat = torch.empty(self.depth, 2 * R * D + R + D, device=dev)                  # the kernels write every element
+        dad = []
+        for row in flat.unbind(0):
+            dad += [row[:R * D].view(R, D), row[R * D:R * D + R], row[R * D + R:2 * R * D + R].view(D, R), row[2 * R * D + R:]]
+        aarr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in dad])
+        call("clhip_vit_backward_adapter", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
+             dprompt.data_ptr() if want_prompt else None, arr, aarr, _st())
+        return dprompt, dl, dad
 
     # --------------------------------------------------------------------------------------- public forward
     def _gram_buffer(self, dev):
@@ -391,7 +451,8 @@ class VisionTransformer(nn.Module):
 
     def features(self, images, prompt_tokens=None, get_input_matrix=False, gram_out=None):
         """[B, D] fp32: final-LN output at the cls token, or (with L2P prompt tokens [P, D]) the mean over the P prompt
-        token outputs (transformer.py:2254-2261).  Differentiable w.r.t. prompt_tokens and the lora_B weights.
+        token outputs (transformer.py:2254-2261).  Differentiable w.r.t. prompt_tokens, the lora_B weights and the adapter tensors; the adapters'
+        dropout is on while the module is in training mode (its seed of the last forward: `last_dropout_seed`).
         get_input_matrix: every layer's X^T X (X = the attention input) is ADDED to a device-resident [depth, D, D] fp32 buffer by one
         MFMA launch at the end of the forward -- the modules' own (`cur_matrix`, read lazily) or the caller's `gram_out`."""
         gram = None
@@ -401,8 +462,12 @@ class VisionTransformer(nn.Module):
         if self.lora_rank and any(a.apply_lora for a in self.attention_modules()):
             for a in self.attention_modules():
                 lora_b += [a.lora_B_k.weight, a.lora_B_v.weight]
-        need = torch.is_grad_enabled() and ((prompt_tokens is not None and prompt_tokens.requires_grad) or any(b.requires_grad for b in lora_b))
-        feat = _VitFn.apply(self, images, prompt_tokens, gram, need, *lora_b)
+        adapters = self.adapter_tensors()
+        if not (torch.is_grad_enabled() and any(t.requires_grad for t in adapters)):
+            adapters = []                                    # frozen adapters still run in the forward; they just are no autograd inputs
+        need = torch.is_grad_enabled() and ((prompt_tokens is not None and prompt_tokens.requires_grad) or any(b.requires_grad for b in lora_b)
+                                            or bool(adapters))
+        feat = _VitFn.apply(self, images, prompt_tokens, gram, need, len(lora_b), *lora_b, *adapters)
         if get_input_matrix and gram_out is None:
             # the running mean over tokens (transformer.py:241-244) is taken when `cur_matrix` is read; here only the token count moves
             cnt = images.shape[0] * (self.patch_embed.num_patches + 1 + (0 if prompt_tokens is None else prompt_tokens.shape[0]))
@@ -560,7 +625,10 @@ def vit_pt_imnet(pretrained=False, **kwargs):
 
 def vit_pt_imnet_in21k_adapter(pretrained=False, **kwargs):
     """the backbone name of the reference's RanPAC config (config/ranpac.yaml:48-52; core/model/backbone/vit.py ViT_in21k_adapter).  Its AdaptFormer
-    adapters start as the identity (`up_proj` is zero-initialised, petl/adapter.py:45-50) and only first-session training moves them, which
-    model/ranpac.py does not implement: the frozen network is the plain ViT-B/16 with the ImageNet-21k weights."""
+    adapters start as the identity (`up_proj` is zero-initialised, petl/adapter.py:45-50) and only first-session training moves them, so without
+    the kwarg `ffn_adapt: true` this is the plain frozen ViT-B/16 with the ImageNet-21k weights.  With it (and `ffn_num`, `ffn_adapter_scalar`,
+    `adapter_dropout`, the names of the reference's tuning config, core/model/backbone/vit.py:152-167) every block gets
+    `adaptmlp.{down_proj, up_proj}`, the block LayerNorms use eps 1e-6 and only the adapters require grad: what RanPAC's
+    `first_session_training: true` trains (csrc/adapter.hip inside the executor)."""
     kwargs.setdefault("model_name", "vit_base_patch16_224_in21k")
     return ViTZoo(pretrained, **kwargs)

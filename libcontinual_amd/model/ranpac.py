@@ -3,7 +3,8 @@
 A frozen pre-trained ViT, a fixed random projection `W_rand` [feat_dim, M] with a ReLU, and a ridge-regression head that is solved, not trained:
 after every task the projected features of the task's training set update two running sums, G = H^T H [M, M] and Q = H^T Y [M, classes], the ridge
 parameter is picked out of 10^-8 .. 10^8 on a 20 % hold-out of the task, and Wo = solve(G + ridge I, Q)^T becomes the head (ranpac.py:214-266).
-There is no per-step backward: `observe` returns a zero loss that requires grad, so the trainer's backward / step are no-ops (ranpac.py:184-186).
+Without first-session training there is no per-step backward: `observe` returns a zero loss that requires grad, so the trainer's backward / step are
+no-ops (ranpac.py:184-186).
 
 Kept from the reference: constructor kwargs, hook order, the fresh cosine head at every `before_task` (so a validation between `before_task` and
 `after_task` scores with a random cosine head), `W_rand` drawn on the CPU from the global generator (a seed reproduces the reference's matrix), Q growing
@@ -11,9 +12,12 @@ by `inc_cls_num` columns per task, the loader's dataset switched to the test tra
 the fitting part of the ridge search, numpy's first-minimum rule, `weight.data = Wo[:classes]`.
 Different by design: features, H, G, Q and the solves live on the device in fp32 (the reference moves everything to the CPU after the forward);
 G and Q are formed as G_val + G_rest / Q_val + Q_rest instead of a third pass over all rows.
-Out of scope: first-session adapter training (AdaptFormer forward / backward inside the ViT executor, with dropout): `first_session_training: true`
-raises at construction.  The reference's adapters start as the identity (`up_proj` is zero-initialised, petl/adapter.py:45-50), so without that
-session the network is exactly the plain ViT-B/16 that `vit_pt_imnet_in21k_adapter` returns.
+First-session training (`first_session_training: true`, the reference's shipped setting; ranpac.py:176-199): task 0 is trained with SGD on the
+cross-entropy of the cosine head's logits, and what moves are the head and the AdaptFormer adapters of the backbone (`ffn_adapt: true` on
+`vit_pt_imnet_in21k_adapter`; forward, input gradient and parameter gradients in csrc/adapter.hip inside the ViT executor, dropout in training mode).
+From `after_task(0)` on the backbone runs in eval mode and every later task only solves the ridge head, on features the trained adapters take part
+in.  The reference's adapters start as the identity (`up_proj` is zero-initialised), so without that session -- or on a backbone built without
+`ffn_adapt`, where the switch raises -- the network is exactly the plain ViT-B/16.
 """
 import math
 import os
@@ -166,18 +170,20 @@ def _eval_view(train_loader, test_trfms, device):
 
 
 class RanPAC(nn.Module):
-    cuda_graph_safe = False        # the step is a no-op; nothing to capture
+    cuda_graph_safe = False        # later tasks: the step is a no-op; the first session: the host draws a dropout seed and re-arms the executor per forward
     reduces_own_gradients = True   # parallel.attach then hands a data-parallel reducer to the plugin, whose setter below refuses it
     _grad_reducer = None
 
     def __init__(self, backbone, device, **kwargs):
         super().__init__()
-        if kwargs.get("first_session_training", False):
-            raise NotImplementedError("RanPAC: `first_session_training: true` (AdaptFormer training of the first session inside the ViT executor) is not "
-                                      "implemented; set first_session_training: false")
+        fst = bool(kwargs.get("first_session_training", False))
+        adapters = getattr(getattr(backbone, "feat", None), "adapter_tensors", lambda: [])()
+        if fst and not adapters:
+            raise NotImplementedError("RanPAC: `first_session_training: true` trains the AdaptFormer adapters of the backbone, and this backbone has none; "
+                                      "build it with the backbone kwarg `ffn_adapt: true`, or set first_session_training: false")
         self._network = Network(backbone, device, **kwargs)
         self.device = device
-        self.first_session_training = False
+        self.first_session_training = fst
         self.init_cls_num, self.inc_cls_num = kwargs["init_cls_num"], kwargs["inc_cls_num"]
         self.total_cls_num, self.task_num = kwargs["total_cls_num"], kwargs["task_num"]
         self.M = kwargs["M"]
@@ -185,8 +191,11 @@ class RanPAC(nn.Module):
         self._classes_seen_so_far = 0
         self._skip_train = False
         self.rp = None
-        for p in self._network.backbone.parameters():      # the frozen pre-trained network: nothing of it ever reaches the optimizer
+        for p in self._network.backbone.parameters():      # the frozen pre-trained network: nothing of it ever reaches the optimizer ...
             p.requires_grad_(False)
+        if fst:
+            for p in adapters:                              # ... but the adapters, in the first session (vision_transformer_adapter.py:461-466)
+                p.requires_grad_(True)
         self._network.to(self.device)
 
     # a data-parallel run would leave every rank with the G / Q of its own shard of the task
@@ -210,12 +219,19 @@ class RanPAC(nn.Module):
         else:
             self._classes_seen_so_far += self.inc_cls_num
         self._network.update_classifer(self._classes_seen_so_far, train_loader)
-        self._skip_train = True                             # ranpac.py:176-180 with first_session_training off
+        self._skip_train = not (task_idx == 0 and self.first_session_training)              # ranpac.py:176-180
+        if self.first_session_training:
+            for p in self._network.backbone.feat.adapter_tensors():                         # after the first session the whole backbone is frozen
+                p.requires_grad_(task_idx == 0)
 
     def observe(self, data):
         if self._skip_train:
             return None, 0., torch.tensor(0., device=self.device, requires_grad=True)        # ranpac.py:184-186
-        raise NotImplementedError("RanPAC: first_session_training is not implemented")
+        x, y = data["image"].to(self.device), data["label"].to(self.device) - self._known_classes                     # ranpac.py:188-199
+        logits = self._network(x)
+        aux = ops.LossAux()                                 # cross-entropy, its gradient, the predictions and the correct count: one launch
+        loss = ops.classify_loss(logits, y, aux=aux)
+        return aux.pred, aux.acc(), loss
 
     def inference(self, data):
         x, y = data["image"].to(self.device), data["label"].to(self.device)
