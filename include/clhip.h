@@ -706,6 +706,26 @@ size_t clhip_rp_classify_ws_bytes(int B, int M, int C);
 int clhip_rp_classify(const float* X, const float* W, const float* Wo, const float* sigma /*nullable*/, float* logits, void* ws, int B, int D, int M,
                       int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * InfLoRA_OPT classifier alignment (core/model/InfLoRA_opt.py:371-456) in exact fp32 on the f32-input MFMA (csrc/ca.hip), under the rules of the
+ * RanPAC kernels: fp32, row-major, dense; no atomics, summation order a function of the shapes only; any D, C, S >= 1.
+ * class_moments: the Gaussians of InfLoRA_opt.py:392-397.  F [N, D] holds the feature rows grouped by class, offsets int32 [C + 1] on the device
+ *             (offsets[0] = 0, offsets[C] = N) where each class starts.  mean [C, D] = the column means of the class's rows, summed in row order
+ *             (:396); cov [C, D, D] = sum (x - mean)(x - mean)^T / (n_c - 1) + eps on the diagonal (:397, torch.cov's unbiased estimate).  The mean is
+ *             subtracted as the rows enter LDS; only the tiles on or above the diagonal are computed and each is written to both places, so cov[c]
+ *             is exactly symmetric.  The offsets are read back and checked on the host (this call synchronises the stream): a class with fewer than
+ *             2 rows, offsets that do not increase, offsets[0] != 0 or offsets[C] != N return CLHIP_EINVAL before anything is launched.
+ * ca_sample : the draws of InfLoRA_opt.py:418-437 for C classes with S rows each, given the Cholesky factors chol [C, D, D] (lower, row-major) and
+ *             standard normals Z [C * S, D]:  X[dest[c * S + s], j] = scale[c] * mean[c, j] + sum_{k <= j} Z[c * S + s, k] * chol[c, j, k]
+ *             (MultivariateNormal.sample = loc + L z with loc = mean * (0.9 + decay), :421-427) and labels[dest[c * S + s]] = class_lo + c (:429);
+ *             dest is the place of a row after the shuffle of :435-437.  One triangular product per class: K blocks above the diagonal are skipped,
+ *             and the strict upper triangle of chol is never read.  dest int64 [C * S] must be a permutation of [0, C * S): otherwise the call
+ *             returns CLHIP_EINVAL with X untouched (checked on the device, with `labels` as the scratch of the check; this call synchronises
+ *             the stream). */
+int clhip_class_moments(const float* F, const int32_t* offsets, float* mean, float* cov, int N, int D, int C, float eps, void* stream);
+int clhip_ca_sample(const float* mean, const float* scale, const float* chol, const float* Z, const int64_t* dest, float* X, int64_t* labels, int C,
+                    int S, int D, int64_t class_lo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

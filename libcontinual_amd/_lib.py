@@ -205,6 +205,8 @@ _PROTOS = {
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "clhip_rp_classify_ws_bytes": (_sz, [_i, _i, _i]),
     "clhip_rp_classify": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "clhip_class_moments": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
+    "clhip_ca_sample": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _p]),
 }
 
 _CHECKED = {}

@@ -10,7 +10,11 @@ Hot loop (observe / backward / step) = HIP: effective-qkv refresh, one backbone 
 backward producing the 24 dB matrices through the rank-r shortcut.  Per-task host logic (SVD of 768x768 Grams,
 DualGPM thresholds) stays on the host in torch / numpy exactly where the reference runs it (InfLoRA_opt.py:251-369);
 the Gram itself (X^T X per layer, transformer.py:241-244) is accumulated on the device by the executor.
-The CLIP branch and classifier alignment (`use_ca`) are outside the hot-path scope.
+Classifier alignment (`use_ca: true`, InfLoRA_opt.py:285-288, :371-456): after every task a Gaussian per class over the backbone features, from
+task 1 on all heads so far re-trained on draws from them -- class_align.ClassAligner on the kernels of csrc/ca.hip.  Two quirks of the reference
+are guards here: with any dataset but cifar100 its loss branch is an empty `pass` (:445-447) and the first step fails on an undefined `loss`; and
+both functions index classes as if init_cls_num == inc_cls_num (:377-381, :418-419).  The feature width is `embd_dim`, not the reference's literal 768.
+The CLIP branch is outside the hot-path scope.
 """
 import math
 import os
@@ -22,6 +26,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils import device_svd
 from .backbone.vit import MultiHeadAttention_LoRA, ViTZoo
+from .class_align import ClassAligner
 from .heads import HipLinear
 
 
@@ -69,8 +74,17 @@ class InfLoRA_OPT(nn.Module):
         self.feature_list = []
         self.project_type = []
         self._dataset = kwargs.get("dataset")
-        if kwargs.get("use_ca", False):
-            raise NotImplementedError("classifier alignment (use_ca) is outside the hot-path scope (SURVEY.md section 8)")
+        self._use_class_alignment = bool(kwargs.get("use_ca", False))
+        self._aligner = None
+        if self._use_class_alignment:
+            if self._dataset != "cifar100":
+                raise NotImplementedError(f"use_ca with dataset {self._dataset!r}: the reference sets _logit_norm = 0.1 for every dataset but cifar100 and that "
+                                          "branch of _compact_classifier is an empty `pass` (InfLoRA_opt.py:158, :445-447): its first step fails on an "
+                                          "undefined `loss`")
+            if self.init_cls_num != self.inc_cls_num:
+                raise NotImplementedError(f"use_ca with init_cls_num {self.init_cls_num} != inc_cls_num {self.inc_cls_num}: _create_distribution and "
+                                          "_compact_classifier index classes as if the two were equal (InfLoRA_opt.py:377-381, :418-419)")
+            self._aligner = ClassAligner(kwargs["embd_dim"], device)
         self._network = SiNet(backbone, device, **kwargs).to(self.device)
         self.attention_modules = [m for m in self._network.modules() if isinstance(m, MultiHeadAttention_LoRA)]
 
@@ -121,6 +135,38 @@ class InfLoRA_OPT(nn.Module):
         for module in self.attention_modules:
             module.merge_weight()
         self._update_feature(task_idx, train_loader, None)
+        if self._use_class_alignment:                                       # InfLoRA_opt.py:285-288
+            self._create_distribution(train_loader, test_loaders[0].dataset.trfms)
+            if task_idx > 0:
+                self._compact_classifier(task_idx)
+
+    # the reference's attribute names (InfLoRA_opt.py:159-160, :385-390), as views of the aligner's state
+    @property
+    def _class_means(self):
+        return self._aligner.means if self._aligner is not None and self._aligner.means.shape[0] else None
+
+    @property
+    def _class_covs(self):
+        return self._aligner.covs if self._aligner is not None and self._aligner.covs.shape[0] else None
+
+    @torch.no_grad()
+    def _create_distribution(self, train_loader, test_trfms):
+        """InfLoRA_opt.py:371-397: eval forward of the task's training set under the test transforms, then mean and covariance per class.  Features are
+        collected batch by batch (the reference keeps the task's images resident and forwards one class at a time)."""
+        from .ranpac import _eval_view
+        self._network.eval()
+        feats, labels = [], []
+        for batch in _eval_view(train_loader, test_trfms, self.device):
+            feats.append(self._network.get_feature(batch["image"].to(self.device)).float())
+            labels.append(batch["label"].to(self.device))
+        self._aligner.add_task(torch.cat(feats, dim=0), torch.cat(labels, dim=0), self._known_classes, self.inc_cls_num)
+
+    def _compact_classifier(self, task_idx):
+        """InfLoRA_opt.py:399-456"""
+        heads = self._network.classifier_pool[: task_idx + 1]
+        for param in heads.parameters():
+            param.requires_grad_(True)
+        self._aligner.align(list(heads), task_idx, self.inc_cls_num)
 
     @torch.no_grad()
     def _update_feature(self, task_idx, train_loader, test_trfms):

@@ -442,6 +442,54 @@ def rp_classify(x, w_rand, wo, sigma=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ classifier alignment (csrc/ca.hip, same arithmetic)
+def class_moments(feats_sorted, offsets, eps):
+    """(mean [C, D], cov [C, D, D]) of the classes whose rows lie back to back in `feats_sorted` [N, D], class c in rows offsets[c] .. offsets[c + 1]:
+    cov = torch.cov's unbiased estimate + eps I (InfLoRA_opt.py:396-397).  A class with fewer than 2 rows raises."""
+    f = _f32c(feats_sorted)
+    offsets = offsets.to(device=f.device, dtype=torch.int32).contiguous()
+    _dev(f, offsets)
+    (N, D), C = f.shape, offsets.numel() - 1
+    mean = torch.empty(C, D, device=f.device, dtype=torch.float32)
+    cov = torch.empty(C, D, D, device=f.device, dtype=torch.float32)
+    call("clhip_class_moments", _ptr(f), _ptr(offsets), _ptr(mean), _ptr(cov), N, D, C, float(eps), _st())
+    return mean, cov
+
+
+def ca_sample(mean, scale, chol, z, dest, class_lo):
+    """(X [C * S, D], labels int64 [C * S]): row c * S + s of the draws scale[c] * mean[c] + z[c * S + s] @ chol[c]^T goes to row dest[c * S + s] with
+    the label class_lo + c (InfLoRA_opt.py:418-437).  `chol` [C, D, D] is read on and below the diagonal only; a `dest` that is no permutation raises."""
+    mean, scale, chol, z = _f32c(mean), _f32c(scale), _f32c(chol), _f32c(z)
+    dest = dest.to(device=mean.device, dtype=torch.int64).contiguous()
+    _dev(mean, scale, chol, z, dest)
+    C, D = mean.shape
+    S = z.shape[0] // C
+    assert tuple(chol.shape) == (C, D, D) and tuple(z.shape) == (C * S, D) and scale.numel() == C and dest.numel() == C * S
+    X = torch.empty(C * S, D, device=mean.device, dtype=torch.float32)
+    labels = torch.empty(C * S, device=mean.device, dtype=torch.int64)
+    call("clhip_ca_sample", _ptr(mean), _ptr(scale), _ptr(chol), _ptr(z), _ptr(dest), _ptr(X), _ptr(labels), C, S, D, int(class_lo), _st())
+    return X, labels
+
+
+def head_sgd_step(x, y, w, b, mom_w, mom_b, lr, momentum, weight_decay, ws=None):
+    """one SGD step of a linear head on the mean cross-entropy of (x [B, D], y [B]) without autograd: clhip_linear_fwd, clhip_ce_window (loss and
+    d loss / d logits), clhip_linear_bwd, clhip_sgd_step_multi -- four launches, w [O, D] / b [O] and their momentum buffers updated in place
+    (InfLoRA_opt.py:443-454).  `ws`: the dict a first call returns (logits, dlogits, dw, db, loss), reused by later calls of the same shapes."""
+    import ctypes as C
+    _dev(x, y, w, b, mom_w, mom_b)
+    (B, D), O = x.shape, w.shape[0]
+    if ws is None:
+        new = lambda *s: torch.empty(*s, device=x.device, dtype=torch.float32)
+        ws = {"logits": new(B, O), "dlogits": new(B, O), "dw": new(O, D), "db": new(O), "loss": new(1)}
+    call("clhip_linear_fwd", _ptr(x), _ptr(w), _ptr(b), _ptr(ws["logits"]), B, D, O, _st())
+    call("clhip_ce_window", _ptr(ws["logits"]), _ptr(y), B, O, 0, O, 0, O, 1.0, _ptr(ws["loss"]), 0, _ptr(ws["dlogits"]), 0, None, None, _st())
+    call("clhip_linear_bwd", _ptr(x), _ptr(w), _ptr(ws["dlogits"]), None, _ptr(ws["dw"]), _ptr(ws["db"]), B, D, O, 0, _st())
+    n = (C.c_int64 * 2)(w.numel(), b.numel())
+    call("clhip_sgd_step_multi", 2, _ptr_array([w, b]), _ptr_array([ws["dw"], ws["db"]]), _ptr_array([mom_w, mom_b]), n, float(lr), float(momentum),
+         float(weight_decay), 1.0, _st())
+    return ws
+
+
 def herding_select(feats_normed, m):
     """indices (int32 tensor [min(m,n)]) chosen by the greedy mean-matching of linearherdingbuffer.py:140-161."""
     f = _f32c(feats_normed)
