@@ -620,6 +620,26 @@ int clhip_adapter_wgrad(const void* gy, const void* hd, const void* x, const voi
                         float* d_down_b, void* ws, float scale, int M, int D, int R, int dtype, void* stream);
 int clhip_adapter_dropout_mask(const unsigned long long* seed, int layer, int M, int R, float p, unsigned char* out, void* stream);
 
+/* SD-LoRA (core/model/sd_lora.py; MultiHeadAttention_SDLoRA, core/model/backbone/transformer.py:276-357; csrc/sdlora.hip).  Per attention layer and for
+ * q and v separately the low-rank branch is a sum over nterms = T + 1 terms: term i has rank ranks[i] (HOST array, each 1..16, sum <= 512; ranks may
+ * differ), A_i [r_i, D] and B_i [D, r_i] fp32.  The factor table of a layer is 4 * nterms DEVICE-resident pointers [A^q terms | B^q terms | A^v
+ * terms | B^v terms]; `factors` of the refresh holds one such table per layer, back to back.  mag [nterms] and inv [layers, 2, nterms] (q then v;
+ * inv of the current term = 1, of a past term 1 / (|B_i|_F |A_i|_F) or 0) are device vectors; c_i = mag[i] * inv[l, w, i].  D % 64 == 0, any M >= 1.
+ * refresh: replaces qq / vv of transformer.py:317-336 by the effective weight W + sum_i c_i B_i A_i on the q and v rows of wt [3D, D] and wt_t
+ *          [D, 3D] (compute dtype) of ALL layers in one launch: fp32 accumulation in term order 0..T, one rounding on the store; k rows untouched.
+ * grad   : replaces autograd through transformer.py:317-332 for one layer: with X [M, D] the attention input and dQ / dV the q / v column blocks of
+ *          dqkv [M, 3D], P_i = X A_i^T, S_i = dQ^T P_i:  d_b = m_T S_T [D, r_T], d_a = m_T (dQ B_T)^T X [r_T, D] (q and v), and
+ *          d_mag_row[i] = sum_{q, v} inv_i <S_i, B_i>_F, this layer's row of partials.  All outputs are WRITTEN.  The K = D products run on the MFMA GEMM
+ *          and the K = M products on the bf16 MFMA (plain FMA in fp32 mode), as slab partials reduced in slab order: no atomics, bitwise reproducible.
+ *          ws: clhip_sdlora_grad_ws_bytes(M, D, sum of ranks) bytes.
+ * mag_reduce: d_mag [nterms] = the rows [depth, nterms] summed in layer order. */
+int clhip_sdlora_refresh(int layers, const float* const* qkv_w, const float* const* factors, const int* ranks, int nterms, const float* mag,
+                         const float* inv, void* const* wt, void* const* wt_t, int D, int dtype, void* stream);
+size_t clhip_sdlora_grad_ws_bytes(int M, int D, int sum_r);
+int clhip_sdlora_grad(const void* x, const void* dqkv, const float* const* factors, const int* ranks, int nterms, const float* mag, const float* inv,
+                      float* d_a_q, float* d_b_q, float* d_a_v, float* d_b_v, float* d_mag_row, void* ws, int M, int D, int dtype, void* stream);
+int clhip_sdlora_mag_reduce(const float* rows, int depth, int nterms, float* d_mag, void* stream);
+
 /* Whole-backbone executor: one C call per forward / backward (VisionTransformer.forward, transformer.py:2222-2294, and
  * the autograd backward of L2P.observe / the trainer's loss.backward()). */
 typedef struct clhip_vit_desc {
@@ -662,6 +682,17 @@ int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long long* seed, 
  * d up_b [D] per layer), nullable.  With adapters the input gradient of every adapter branch is part of the chain either way. */
 int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                                float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream);
+/* SD-LoRA mode of the executor (new entry points; descriptors and parameter tables are untouched, so every other caller gets the executor it had).
+ * set_sdlora: nterms > 0 switches the mode on -- ranks (host, copied), factors = [depth] factor tables back to back, mag [nterms], inv [depth, 2,
+ *          nterms] on the device, all alive until replaced; forwards that save for the backward then keep every layer's attention input.  nterms = 0
+ *          switches it off.  Requires lora_rank == 0 in the descriptor.
+ * sdlora_refresh: clhip_sdlora_refresh on the executor's qkv copies (after clhip_vit_prep_weights without LoRA, and then once per step).
+ * backward_sdlora: clhip_vit_backward that also runs clhip_sdlora_grad per layer: d_factors = [4 * depth] pointers (d A_q, d B_q, d A_v, d B_v of the
+ *          current term per layer), d_mag_rows [depth, nterms] scratch, d_mag [nterms] = its rows summed in layer order. */
+int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, const float* const* factors, const float* mag, const float* inv);
+int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream);
+int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                              float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream);
 /* debug/test: copy one saved activation of layer l (0 x_in, 1 qkv, 2 attn out, 3 x_mid, 4 GELU derivative of the mlp) to fp32 */
 int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream);
 

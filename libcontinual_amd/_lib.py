@@ -200,6 +200,13 @@ _PROTOS = {
     "clhip_adapter_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
     "clhip_adapter_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _p]),
     "clhip_adapter_dropout_mask": (_i, [_p, _i, _i, _i, _f, _p, _p]),
+    "clhip_sdlora_refresh": (_i, [_i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "clhip_sdlora_grad_ws_bytes": (_sz, [_i, _i, _i]),
+    "clhip_sdlora_grad": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clhip_sdlora_mag_reduce": (_i, [_p, _i, _i, _p, _p]),
+    "clhip_vit_set_sdlora": (_i, [_p, _i, _p, _p, _p, _p]),
+    "clhip_vit_sdlora_refresh": (_i, [_p, C.POINTER(VitParams), _p, _p]),
+    "clhip_vit_backward_sdlora": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),

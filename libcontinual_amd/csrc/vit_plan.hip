@@ -20,7 +20,7 @@ struct LayerShadow { size_t qkv_f, qkv_b, proj_f, proj_b, fc1_f, fc1_b, fc2_f, f
 
 struct Layout {          // byte offsets into the workspace for one (B, n_prompt, save) configuration
     int B, P, N, M, save;
-    size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, g2, ad_dh, ad_ws, total;
+    size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, g2, ad_dh, ad_ws, sd_ws, total;
     std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse, ad_hd;   // per layer (x_in has depth+1 entries)
 };
 
@@ -42,6 +42,10 @@ struct clhip_vit {
     const unsigned long long* drop_seed;   // adapter dropout of the next forward (clhip_vit_set_adapter_dropout) ...
     float drop_p;
     float last_p;                          // ... and of the forward the backward belongs to
+    int sd_terms, sd_sum;                  // SD-LoRA mode (clhip_vit_set_sdlora): term count (0 = off), sum of the ranks ...
+    std::vector<int> sd_ranks;
+    const float* const* sd_factors;        // ... and the caller's device tables
+    const float *sd_mag, *sd_inv;
 };
 
 // `flags`: bit 0 = keep what the backward needs; bit 1 (CLHIP_VIT_KEEP_ATTN_IN) = keep every layer's attention input (LN1 output) until the
@@ -61,7 +65,7 @@ static void make_layout(const clhip_vit* v, int B, int P, int flags, Layout& L) 
     const int sets = save ? d.depth : 1;
     L.x_in.assign(d.depth + 1, 0); L.x_mid.assign(d.depth, 0); L.qkv.assign(d.depth, 0); L.attn_o.assign(d.depth, 0);
     L.hpre.assign(d.depth, 0); L.h1.assign(d.depth, 0); L.st1.assign(d.depth, 0); L.st2.assign(d.depth, 0); L.lse.assign(d.depth, 0);
-    const bool keep_h1 = save && d.lora_rank > 0;
+    const bool keep_h1 = save && (d.lora_rank > 0 || v->sd_terms > 0);
     for (int s = 0; s < sets; ++s) {
         L.x_mid[s] = take(M * D * e);
         L.qkv[s] = take(M * 3 * D * e);
@@ -106,6 +110,7 @@ static void make_layout(const clhip_vit* v, int B, int P, int flags, Layout& L) 
         L.g2 = take(M * D * e);
         L.ad_ws = take(clhip_adapter_wgrad_ws_bytes(L.M, d.dim, d.adapter_dim));
     }
+    L.sd_ws = save && v->sd_terms > 0 ? take(clhip_sdlora_grad_ws_bytes(L.M, d.dim, v->sd_sum)) : 0;      // (appended, like the adapters' part)
     L.total = off;
 }
 
@@ -138,6 +143,7 @@ extern "C" clhip_vit* clhip_vit_create(const clhip_vit_desc* desc, int dtype) {
     v->shadow_bytes = off;
     v->have_last = false;
     v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = 0.f;
+    v->sd_terms = v->sd_sum = 0; v->sd_factors = nullptr; v->sd_mag = v->sd_inv = nullptr;
     return v;
 }
 
@@ -165,6 +171,29 @@ extern "C" int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long l
     CLHIP_CHECK_ARG((p > 0.f) == (seed != nullptr));
     v->drop_seed = seed; v->drop_p = p;
     return CLHIP_OK;
+}
+
+extern "C" int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, const float* const* factors, const float* mag, const float* inv) {
+    CLHIP_CHECK_ARG(v && nterms >= 0 && v->d.lora_rank == 0);
+    if (nterms == 0) { v->sd_terms = v->sd_sum = 0; v->sd_ranks.clear(); v->sd_factors = nullptr; v->sd_mag = v->sd_inv = nullptr; v->have_last = false; return CLHIP_OK; }
+    CLHIP_CHECK_ARG(ranks && factors && mag && inv && nterms <= 512);
+    int sum = 0;
+    for (int i = 0; i < nterms; ++i) { CLHIP_CHECK_ARG(ranks[i] >= 1 && ranks[i] <= 16); sum += ranks[i]; }
+    CLHIP_CHECK_ARG(sum <= 512);
+    v->sd_terms = nterms; v->sd_sum = sum; v->sd_ranks.assign(ranks, ranks + nterms);
+    v->sd_factors = factors; v->sd_mag = mag; v->sd_inv = inv;
+    v->have_last = false;                                    // a saved forward of another term set cannot be continued
+    return CLHIP_OK;
+}
+
+extern "C" int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream) {
+    CLHIP_CHECK_ARG(v && P && P->layers && shadow && v->sd_terms > 0);
+    char* sh = static_cast<char*>(shadow);
+    const int n = v->d.depth;
+    std::vector<const float*> w(n);
+    std::vector<void*> wt(n), wtt(n);
+    for (int l = 0; l < n; ++l) { w[l] = P->layers[l].qkv_w; wt[l] = sh + v->sh[l].qkv_f; wtt[l] = sh + v->sh[l].qkv_b; }
+    return clhip_sdlora_refresh(n, w.data(), v->sd_factors, v->sd_ranks.data(), v->sd_terms, v->sd_mag, v->sd_inv, wt.data(), wtt.data(), v->d.dim, v->dtype, stream);
 }
 
 extern "C" int clhip_vit_prep_weights(clhip_vit* v, const clhip_vit_params* P, void* shadow, int apply_lora, int qkv_only, void* stream) {
@@ -256,9 +285,26 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
     return clhip_vit_backward_adapter(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, stream);
 }
 
+static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, void* stream);
+
 extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                                           float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream) {
+    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, d_adapter, nullptr, nullptr, stream);
+}
+
+extern "C" int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
+                                         float* dprompt_tokens, float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream) {
+    CLHIP_CHECK_ARG(v && v->sd_terms > 0 && d_factors && d_mag_rows && d_mag);
+    TRY(backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, d_factors, d_mag_rows, stream));
+    return clhip_sdlora_mag_reduce(d_mag_rows, v->d.depth, v->sd_terms, d_mag, stream);
+}
+
+// d_sd (nullable): the SD-LoRA gradients, run where the lora_B gradients run (the two modes exclude each other)
+static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && dfeat);
+    CLHIP_CHECK_ARG(d_sd == nullptr || (v->sd_terms > 0 && d_lora_b == nullptr && v->last.sd_ws != 0));
     CLHIP_CHECK_ARG(d_adapter == nullptr || v->d.adapter_dim > 0);
     CLHIP_CHECK_ARG(v->have_last && v->last.save);
     const clhip_vit_desc& d = v->d;
@@ -277,7 +323,7 @@ extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* 
     // (inside a stream capture everything stays on the captured stream, as plan.hip does: no fork / join nodes, no stream probe)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(main_s, &cap);
-    const bool side_on = two_streams && d_lora_b != nullptr && cap == hipStreamCaptureStatusNone;
+    const bool side_on = two_streams && (d_lora_b != nullptr || d_sd != nullptr) && cap == hipStreamCaptureStatusNone;
     hipStream_t shared_side = side_on ? clhip_shared_stream(0, main_s, false) : nullptr;
     if (side_on && shared_side == nullptr) { clhip_set_error("clhip_vit_backward: cannot create the side stream"); return CLHIP_EHIP; }
     const bool first_side = side_on && !v->side;
@@ -325,6 +371,20 @@ extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* 
             }
             TRY(clhip_lora_grad(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_a_v, sh + s.acat, d_lora_b[2 * l], d_lora_b[2 * l + 1], ws + L.lora_ws, M, D,
                                 d.lora_rank, dt, ls));
+            if (side_on) { (void)hipEventRecord(v->ev_l, v->side); lora_pending = true; }
+        }
+        if (d_sd) {
+            float* const* gs = d_sd + 4 * l;
+            CLHIP_CHECK_ARG(gs[0] && gs[1] && gs[2] && gs[3]);
+            void* ls = stream;
+            if (side_on) {
+                (void)hipEventRecord(v->ev_q, main_s);
+                (void)hipStreamWaitEvent(v->side, v->ev_q, 0);
+                ls = v->side;
+            }
+            TRY(clhip_sdlora_grad(ws + L.h1[l], ws + L.dqkv, v->sd_factors + (size_t)l * 4 * v->sd_terms, v->sd_ranks.data(), v->sd_terms, v->sd_mag,
+                                  v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M, D,
+                                  dt, ls));
             if (side_on) { (void)hipEventRecord(v->ev_l, v->side); lora_pending = true; }
         }
         if (l == 0 && dprompt_tokens == nullptr) break;           // nothing below the first block needs a gradient

@@ -14,4 +14,5 @@ from .l2p import L2P  # noqa: F401
 from .inflora_opt import InfLoRA_OPT  # noqa: F401
 from .inflora import InfLoRA  # noqa: F401
 from .ranpac import RanPAC, RPClassifier  # noqa: F401
+from .sd_lora import SD_LoRA  # noqa: F401
 from .heads import HipLinear  # noqa: F401

@@ -8,6 +8,7 @@ kwargs and plugin code written against it keep working:
         patch_embed.proj, cls_token, pos_embed, transformer.blocks[i].{ln_1, attn.{qkv, proj[, lora_*]}, ln_2, mlp.{fc1, fc2}}, norm
         [ffn_adapt: transformer.blocks[i].adaptmlp.{down_proj, up_proj}   core/model/backbone/petl/vision_transformer_adapter.py:31-90]
     MultiHeadAttention_LoRA    transformer.py:199-274   (apply_lora, init_param, merge_weight, reset_input_matrix, cur_matrix)
+    MultiHeadAttention_SDLoRA  transformer.py:276-357   (lora_{A,B}_{q,v}_list, mag_lora, assimilated_mag_lora_{q,v}, init_param)
     L2PPrompt                  core/model/backbone/prompt.py:345-406 (prompt, prompt_key)
 
 The modules below only OWN parameters (fp32 masters on the device); they have no forward of their own.  All
@@ -148,6 +149,39 @@ class MultiHeadAttention_LoRA(MultiHeadAttention):
         self.cur_matrix.zero_()
 
 
+class MultiHeadAttention_SDLoRA(MultiHeadAttention):
+    """transformer.py:276-357: on q and v a sum over the tasks so far of low-rank terms, the past ones normalised to unit Frobenius norm, each scaled
+    by a trainable scalar of `mag_lora` (a ParameterList the method assigns, the same object in every block).  The lists hold parameter holders, so
+    the names are `...lora_A_q_list.{i}.weight` as in the reference (sd_lora.py:130-136 filters on them).  `lora_rank` is mutable: init_param appends
+    a term of the rank it has then (rank reduction, sd_lora.py:112-119)."""
+
+    def __init__(self, dim, num_heads, lora_rank=10, lora_bias=False, **kw):
+        super().__init__(dim, num_heads)
+        assert not lora_bias
+        self.lora_rank, self.lora_bias = lora_rank, lora_bias
+        self.lora_A_q_list, self.lora_B_q_list = nn.ModuleList([]), nn.ModuleList([])
+        self.lora_A_v_list, self.lora_B_v_list = nn.ModuleList([]), nn.ModuleList([])
+        self.assimilated_mag_lora_q, self.assimilated_mag_lora_v = [], []      # 0 unless knowledge distillation merges a term: never enter the kernels
+
+    def factor_lists(self):
+        return (self.lora_A_q_list, self.lora_B_q_list, self.lora_A_v_list, self.lora_B_v_list)
+
+    def init_param(self):
+        dev, r = self.qkv.weight.device, int(self.lora_rank)
+        for lst, shape in zip(self.factor_lists(), ((r, self.dim), (self.dim, r), (r, self.dim), (self.dim, r))):
+            lst.append(_P(shape, False))
+        nn.init.kaiming_uniform_(self.lora_A_q_list[-1].weight, a=math.sqrt(5))
+        nn.init.kaiming_uniform_(self.lora_A_v_list[-1].weight, a=math.sqrt(5))
+        nn.init.zeros_(self.lora_B_q_list[-1].weight)
+        nn.init.zeros_(self.lora_B_v_list[-1].weight)
+        for lst in self.factor_lists():
+            lst[-1].to(dev)
+        self.assimilated_mag_lora_q.append(torch.zeros(1, device=dev))
+        self.assimilated_mag_lora_v.append(torch.zeros(1, device=dev))
+        assert len(self.lora_A_q_list) == len(self.mag_lora)
+        assert len(self.mag_lora) == len(self.assimilated_mag_lora_q)
+
+
 class Mlp(nn.Module):
     def __init__(self, dim, hidden):
         super().__init__()
@@ -197,7 +231,8 @@ class _PatchEmbed(nn.Module):
         self.proj = _P((embed_dim, in_chans, patch_size, patch_size))
 
 
-_ATTN = {"MultiHeadAttention": MultiHeadAttention, "MultiHeadAttention_LoRA": MultiHeadAttention_LoRA}
+_ATTN = {"MultiHeadAttention": MultiHeadAttention, "MultiHeadAttention_LoRA": MultiHeadAttention_LoRA,
+         "MultiHeadAttention_SDLoRA": MultiHeadAttention_SDLoRA}
 
 
 class _Scratch:
@@ -212,6 +247,8 @@ class _Scratch:
         self.cparams = None
         self.keep = None
         self.gram = None
+        self.sd_key = None        # SD-LoRA: identity of the term set the executor was told about, and its device tables
+        self.sd_tab = self.sd_ranks = self.sd_mag = self.sd_inv = None
 
     def __deepcopy__(self, memo):
         return _Scratch()
@@ -238,6 +275,24 @@ class _VitFn(torch.autograd.Function):
         return (None, None, dprompt, None, None, None) + tuple(dlora if dlora else ()) + tuple(dad if dad else ())
 
 
+class _VitSdFn(torch.autograd.Function):
+    """features = ViT(images) in SD-LoRA mode; `params` = A_q, B_q, A_v, B_v of the current term per layer, then the magnitudes: backward -> their
+    gradients (transformer.py:317-332 under autograd in the reference)"""
+
+    @staticmethod
+    def forward(ctx, vit, images, need, *params):
+        feat = vit._run_forward(images, None, need, None)
+        ctx.vit, ctx.token = vit, vit._fwd_token
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        vit = ctx.vit
+        if vit._fwd_token != ctx.token:
+            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        return (None, None, None) + tuple(vit._run_backward_sd(dfeat))
+
+
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, attn_layer="MultiHeadAttention",
                  mlp_ratio=4.0, dtype="bf16", lora_rank=0, ffn_adapt=False, ffn_num=64, ffn_adapter_scalar=0.1, adapter_dropout=0.1, **kwargs):
@@ -255,7 +310,8 @@ class VisionTransformer(nn.Module):
         self.patch_embed = _PatchEmbed(img_size, patch_size, in_chans, embed_dim)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + 1, embed_dim))
-        kw = {"lora_rank": lora_rank} if self.lora_rank else {}
+        self.sd_lora = attn_layer is MultiHeadAttention_SDLoRA
+        kw = {"lora_rank": lora_rank} if self.lora_rank or self.sd_lora else {}
         self.transformer = Transformer(embed_dim, depth, num_heads, mlp_ratio, attn_layer, **kw)
         self.norm = _P((embed_dim,))
         self._s = _Scratch()
@@ -358,6 +414,8 @@ class VisionTransformer(nn.Module):
         if self.lora_rank:            # lora_A is fixed within a task: a change (init_param / SVD in before_task) forces the full preparation
             for a in self.attention_modules():
                 frozen = frozen + [a.lora_A_k.weight, a.lora_A_v.weight]
+        if self.sd_lora:
+            return self._ensure_sd(s, dev, frozen)
         sig = (tuple((t.data_ptr(), t._version) for t in frozen), lora_on)
         if s.sig != sig:
             call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), int(lora_on), 0, _st())
@@ -366,6 +424,88 @@ class VisionTransformer(nn.Module):
             # lora_B moves every optimizer step: refresh only the effective qkv copies (transformer.py:249-255)
             call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), 1, 1, _st())
         return s
+
+    # ------------------------------------------------------------------------------------ SD-LoRA state
+    def sd_terms(self):
+        return len(self.attention_modules()[0].lora_A_q_list) if self.sd_lora else 0
+
+    def sd_trainable(self):
+        """the autograd inputs of the SD-LoRA mode: A_q, B_q, A_v, B_v of the last term per layer, then the magnitudes"""
+        out = []
+        for a in self.attention_modules():
+            out += [lst[-1].weight for lst in a.factor_lists()]
+        return out + list(self.attention_modules()[0].mag_lora)
+
+    @torch.no_grad()
+    def sdlora_update_inv(self):
+        """inv [depth, 2, T + 1] on the device, no host synchronisation: 1 / (|B_i|_F |A_i|_F) of the past terms (0 where a norm is 0: the reference
+        skips such a term, transformer.py:325, :331) and 1 for the current one.  Constant within a task: sd_lora.SD_LoRA.before_task calls this."""
+        mods, T1 = self.attention_modules(), self.sd_terms()
+        norms = torch.stack([torch.stack([torch.linalg.vector_norm(h.weight) for h in lst]) for a in mods for lst in a.factor_lists()])
+        norms = norms.view(len(mods), 2, 2, T1).double()
+        prod = norms[:, :, 0] * norms[:, :, 1]
+        inv = torch.where(prod != 0, 1.0 / prod, torch.zeros_like(prod)).float()
+        inv[:, :, -1] = 1.0
+        self._s.sd_inv = inv.contiguous()
+        self._s.sd_key = None                                # the executor is handed the new vector at the next forward
+
+    def _ensure_sd(self, s, dev, frozen):
+        """SD-LoRA: the past terms and `inv` are fixed within a task (a change forces the full preparation); the current term and the magnitudes
+        move every optimizer step (the fused optimizers write through raw pointers, so no version counter tells), hence the q / v rows of the
+        effective qkv copies are refreshed before every forward, as the LoRA path does."""
+        mods, T1 = self.attention_modules(), self.sd_terms()
+        if T1 == 0:                                          # no term yet: the plain backbone
+            if s.sd_key is not None:
+                call("clhip_vit_set_sdlora", s.handle, 0, None, None, None, None)
+                s.sd_key, s.sig = None, None
+            sig = (tuple((t.data_ptr(), t._version) for t in frozen), "sd0")
+            if s.sig != sig:
+                call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), 0, 0, _st())
+                s.sig = sig
+            return s
+        if any(len(lst) != T1 for a in mods for lst in a.factor_lists()) or any(a.mag_lora is not mods[0].mag_lora for a in mods) \
+                or len(mods[0].mag_lora) != T1:
+            raise _lib.ClhipError("SD-LoRA: every attention layer needs the same number of terms and the one shared mag_lora list with a scalar per term")
+        ranks = [h.weight.shape[0] for h in mods[0].lora_A_q_list]
+        fact = [[h.weight for h in lst] for a in mods for lst in a.factor_lists()]           # [depth * 4][T1]
+        for a in mods:
+            for la, lb in ((a.lora_A_q_list, a.lora_B_q_list), (a.lora_A_v_list, a.lora_B_v_list)):
+                if [h.weight.shape[0] for h in la] != ranks or [h.weight.shape[1] for h in lb] != ranks:
+                    raise _lib.ClhipError("SD-LoRA: the rank of a term must be the same in every layer and for q and v")
+        past = [t for row in fact for t in row[:-1]]
+        key = (tuple(t.data_ptr() for row in fact for t in row), tuple(ranks), tuple((t.data_ptr(), t._version) for t in past), dev)
+        if s.sd_inv is None or tuple(s.sd_inv.shape) != (self.depth, 2, T1) or s.sd_inv.device != dev:
+            self.sdlora_update_inv()
+        if s.sd_key != key:
+            if s.sd_key is not None and s.sd_key[2] != key[2]:
+                self.sdlora_update_inv()                     # a past term was changed by hand: its norm moved
+            s.sd_tab = torch.tensor([[t.data_ptr() for t in row] for row in fact], dtype=torch.int64).to(dev)
+            s.sd_ranks = (C.c_int * T1)(*ranks)
+            s.sd_mag = torch.empty(T1, device=dev)
+            call("clhip_vit_set_sdlora", s.handle, T1, s.sd_ranks, s.sd_tab.data_ptr(), s.sd_mag.data_ptr(), s.sd_inv.data_ptr())
+            s.sd_key, s.sig = key, None
+        sig = (tuple((t.data_ptr(), t._version) for t in frozen), key[2], "sd")
+        if s.sig != sig:
+            call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), 0, 0, _st())
+            s.sig = sig
+        torch.cat([m.detach().reshape(1) for m in mods[0].mag_lora], out=s.sd_mag)
+        call("clhip_vit_sdlora_refresh", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), _st())
+        return s
+
+    def _run_backward_sd(self, dfeat):
+        s = self._s
+        dfeat = dfeat.float().contiguous()
+        dev, D, T1 = dfeat.device, self.embed_dim, self.sd_terms()
+        r = self.attention_modules()[0].lora_A_q_list[-1].weight.shape[0]
+        flat = torch.empty(self.depth, 4 * r * D, device=dev)                          # the kernels write every element
+        grads = []
+        for row in flat.unbind(0):
+            grads += [row[:r * D].view(r, D), row[r * D:2 * r * D].view(D, r), row[2 * r * D:3 * r * D].view(r, D), row[3 * r * D:].view(D, r)]
+        arr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in grads])
+        rows, dmag = torch.empty(self.depth, T1, device=dev), torch.empty(T1, device=dev)
+        call("clhip_vit_backward_sdlora", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, arr,
+             rows.data_ptr(), dmag.data_ptr(), _st())
+        return grads + [dmag[i:i + 1] for i in range(T1)]
 
     def _workspace(self, s, B, n_prompt, save, dev):
         """`save`: bit 0 = keep what the backward needs, bit 1 = keep every layer's attention input for the Gram launch"""
@@ -458,6 +598,12 @@ class VisionTransformer(nn.Module):
         gram = None
         if get_input_matrix:
             gram = gram_out if gram_out is not None else self._gram_buffer(images.device)
+        if self.sd_lora and self.sd_terms() > 0:
+            if prompt_tokens is not None or get_input_matrix:
+                raise NotImplementedError("SD-LoRA runs without prompt tokens and without the input Gram")
+            params = self.sd_trainable()
+            need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
+            return _VitSdFn.apply(self, images, need, *params)
         lora_b = []
         if self.lora_rank and any(a.apply_lora for a in self.attention_modules()):
             for a in self.attention_modules():
