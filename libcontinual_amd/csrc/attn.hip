@@ -288,8 +288,9 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
 // rate, but in TEN dependent round trips with one workgroup per CU and nothing beside it; + phase A 41 us; + phase B 63 us; PMC: matrix pipes 18 % busy, 59 % of the wave
 // cycles parked in s_waitcnt, no bank conflicts; both phases sit at ~64 B/clk of LDS operand reads).  This form
 //   * makes every global read of the prologue in ONE round trip (151 -> 137 us on the evidence box);
-//   * drops the masks of keys >= N: a padded key's K and V rows are zero in LDS, so whatever finite dS it gets multiplies zeros in dQ (phase A), and in phase B it only
-//     feeds its own output column, which is never stored (14 + 8 compare / select instructions per tile pair).  Padded QUERIES still vanish through lse = +inf;
+//   * drops the masks of keys >= N in phase B, and in phase A in every key-tile pair but the last: a padded key's K and V rows are zero in LDS; in phase B it only
+//     feeds its own output column, which is never stored; in phase A its dS multiplies zero K rows, but it is not always finite (see tileA), so the last pair, which
+//     holds every padded key, keeps the mask (14 + 8 compare / select instructions per tile pair elsewhere).  Padded QUERIES still vanish through lse = +inf;
 //   * requests the next tile's fragments before this tile's arithmetic.
 // The last two measure nothing by themselves (the phases are LDS-bandwidth bound: a two-tiles-per-wave variant that halves the LDS bytes per MFMA needs > 128 registers,
 // i.e. eight waves instead of sixteen, and ran 167 us).  Same MFMAs on the same operands for every stored element: bit-identical to the kernel above (tests).
@@ -383,7 +384,10 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma3_kernel(AttnPara
         for (int dt = 0; dt < 4; ++dt) acc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         uint4 k0[2], v0[2], k1[2], v1[2];
         frag(Ks, Vs, l15, k0, v0);
-        auto tileA = [&](const uint4 (&kf)[2], const uint4 (&vf)[2], f32x4& ds) {
+        // tail (a literal at both call sites): the LAST pair holds every key >= N (N > (NPAIR - 1) * 32) and keeps the mask of the kernel above.  A padded key's
+        // P = exp2(0 - lq) is +inf for a query row with lse < -88.7 (every logit of the row far below zero), dS = inf * (0 - dq) is +-inf or NaN, and inf * 0 in the
+        // dQ MFMA is NaN: "finite dS times zero K rows" does not hold there.  The other NPAIR - 1 pairs stay without compare / select.
+        auto tileA = [&](const uint4 (&kf)[2], const uint4 (&vf)[2], f32x4& ds, const bool tail, const int key0) {
             f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
@@ -391,25 +395,31 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma3_kernel(AttnPara
                 dp = mfma_bf16(vf[kk], gf[kk], dp);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ds[e] = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq)) * (dp[e] - dq);
+            for (int e = 0; e < 4; ++e) {
+                float pr = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
+                if (tail && key0 + e >= N) pr = 0.f;
+                ds[e] = pr * (dp[e] - dq);
+            }
         };
-#pragma unroll 1
-        for (int ks = 0; ks < nPair; ++ks) {
+        auto pairA = [&](const int ks, const bool tail) {
             uint4 kt_[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) kt_[dt] = tr8(Ks, (2 * ks * 16 + g * 4 + (l15 >> 2)) * KP + (dt * 16 + (l15 & 3) * 4) * 2, 16 * KP);
             frag(Ks, Vs, (2 * ks + 1) * 16 + l15, k1, v1);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 ds[2];
-            tileA(k0, v0, ds[0]);
+            tileA(k0, v0, ds[0], tail, 2 * ks * 16 + g * 4);
             __builtin_amdgcn_sched_barrier(0);
-            if (ks + 1 < nPair) frag(Ks, Vs, (2 * ks + 2) * 16 + l15, k0, v0);
+            if (!tail) frag(Ks, Vs, (2 * ks + 2) * 16 + l15, k0, v0);
             __builtin_amdgcn_sched_barrier(0);
-            tileA(k1, v1, ds[1]);
+            tileA(k1, v1, ds[1], tail, (2 * ks + 1) * 16 + g * 4);
             const uint4 db = pack8(ds[0], ds[1]);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) acc[dt] = mfma_bf16(kt_[dt], db, acc[dt]);
-        }
+        };
+#pragma unroll 1
+        for (int ks = 0; ks < nPair - 1; ++ks) pairA(ks, false);
+        pairA(nPair - 1, true);
         if (qrow < N) {
             bf16_t* r = dqb + (size_t)qrow * ld + g * 4;
 #pragma unroll

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import vit_refs
+
 pytestmark = pytest.mark.gpu
 
 from libcontinual_amd import _lib           # noqa: E402
@@ -249,13 +251,18 @@ def test_attention_fwd_bwd(dt, B, N, H, hd):
         assert relerr(dqkv[:, i * D:(i + 1) * D], g[:, i * D:(i + 1) * D]) < (4e-2 if dt == "bf16" else 5e-5), nm
 
 
-@pytest.mark.parametrize("B,N,H", [(5, 197, 12), (2, 222, 3), (3, 17, 2), (2, 240, 1), (2, 33, 2)])
+@pytest.mark.parametrize("B,N,H", [(5, 197, 12), (2, 222, 3), (3, 17, 2), (2, 240, 1), (2, 33, 2), (2, 193, 3), (2, 208, 3), (2, 209, 3), (2, 224, 3), (-2, 197, 3)])
 def test_attention_bwd_variants_are_bit_identical(B, N, H):
     """attn_bwd_mfma3_kernel (one-round-trip prologue, no key masks, read-ahead; 197 / 222 tokens) issues the MFMAs of every stored element on the same operands in the
-    same order as the kernel of rounds 2-5 (ATTN_BWD=1; also the path of every other token count)"""
+    same order as the kernel of rounds 2-5 (ATTN_BWD=1; also the path of every other token count).  B < 0: the shifted-logit input of vit_refs
+    (a query row with lse < -100 next to padded keys, one with lse > +100, a one-hot row, a head of identical keys) at batch -B"""
     D = H * 64
-    qkv = (rnd(B * N, 3 * D, seed=17) * 1.5).to(torch.bfloat16)
-    dout = rnd(B * N, D, seed=18).to(torch.bfloat16)
+    if B < 0:
+        B = -B
+        qkv, dout = (t.to(DEV).to(torch.bfloat16) for t in vit_refs.attn_shifted_inputs(B, N, H, 64, 500 + N))
+    else:
+        qkv = (rnd(B * N, 3 * D, seed=17) * 1.5).to(torch.bfloat16)
+        dout = rnd(B * N, D, seed=18).to(torch.bfloat16)
     out = torch.empty(B * N, D, device=DEV, dtype=torch.bfloat16)
     lse = torch.empty(B, H, N, device=DEV)
     dsum = torch.empty(B, H, N, device=DEV)
