@@ -23,6 +23,14 @@ void clhip_set_error(const char* fmt, ...);
 // Both roles get the SAME stream (they are busy in different halves of a step, and one shared hardware queue measured faster than two: api.hip).
 hipStream_t clhip_shared_stream(int role, hipStream_t main_s, bool low_priority);
 const char* clhip_cfg(const char* name);      // api.hip: value of a configuration switch (clhip_config(), else $CLHIP_<name>), nullptr if unset
+// tn_slab.hip: the K = M products of the LoRA-family weight gradients, one fp32 partial per slab of `rows_per_slab` token rows and no atomics:
+//     slab[s, w, o, j] = sum_{m in row slab s} Y_w[m, o] Z_w[m, j0_w + j]      w < nw, o < O, j < jn
+// Y_w = Y + w * ystep (row pitch ldy), Z_w = Z + w * zstep (row pitch ldz), j0_w = w * j0step, in elements; the windows of all w lie in the rows of ONE Z
+// ((nw - 1) (zstep + j0step) + jn <= ldz).  Z in fp32: plain FMA, Y in either dtype, no column at or beyond j0_w + jn is loaded.  Z in bf16: the MFMA form; Y is
+// bf16 too, O % 64 == 0, pitches and steps are multiples of 8, and Z_w is read in whole 32-column tiles up to the end of the last window, which ldz must cover
+// (for EVERY w: with j0step > 0 the tiles of an earlier window beyond its own end compute and store nothing -- none at r <= 16, where there is one tile).
+int clhip_tn_slabs(const void* Y, int ydtype, int ldy, int ystep, const void* Z, int zdtype, int ldz, int zstep, int j0step, float* slab, int M, int O, int jn,
+                   int nw, int rows_per_slab, hipStream_t s);
 
 #define CLHIP_CHECK_ARG(cond)                                                          \
     do {                                                                               \
@@ -56,6 +64,17 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     f32x2_t v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
+
+// two transposing 8-byte LDS reads (ds_read_b64_tr_b16) -> the 8 reduction elements of one bf16 MFMA operand row; `second` = byte distance of reduction
+// elements k+4..k+7 from k..k+3
+__device__ __forceinline__ uint4 tr8(const char* base, int addr, int second) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
+    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
+    return make_uint4(l.x, l.y, h.x, h.y);
+}
+__device__ __forceinline__ bf16x8_t tr8b(const char* base, int addr, int second) { return __builtin_bit_cast(bf16x8_t, tr8(base, addr, second)); }
 
 // Element traits: T = bf16_t (storage uint16) or float.  A "chunk" is 8 consecutive elements.
 template <typename T> struct Elem;

@@ -1344,15 +1344,6 @@ struct Wgrad3Params {
 
 constexpr int P3 = 144;      // LDS pitch of a 64-channel (128 B) row: 4 consecutive rows fall in disjoint bank ranges
 
-// two transposing 8-byte reads -> 8 reduction elements; `second` = byte distance of reduction elements k+4..k+7
-__device__ __forceinline__ uint4 tr8(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-
 __global__ __launch_bounds__(512) void conv_wgrad3_kernel(Wgrad3Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

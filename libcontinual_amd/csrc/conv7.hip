@@ -205,14 +205,6 @@ namespace {
 
 struct Wgrad7Params { const bf16_t* x; const bf16_t* dz; const bf16_t* dzs; float* slab3; float* slabsc; int N, ipg; };
 
-__device__ __forceinline__ uint4 tr8_7(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-
 template <int C>
 __global__ __launch_bounds__(256) void wgrad7_kernel(const Wgrad7Params p) {
     constexpr int K = 2 * C, W = C == 16 ? 32 : 16, H = W, Wo = W / 2, Ho = H / 2, PW = W + 2;
@@ -263,9 +255,9 @@ __global__ __launch_bounds__(256) void wgrad7_kernel(const Wgrad7Params p) {
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
-            const uint4 zf = tr8_7(zs, zaddr + s * 32 * PZB, 4 * PZB);
+            const uint4 zf = tr8(zs, zaddr + s * 32 * PZB, 4 * PZB);
             uint4 zsf = make_uint4(0, 0, 0, 0);
-            if (C == 32 || t_lo == 5) zsf = tr8_7(zss, zaddr + s * 32 * PZB, 4 * PZB);
+            if (C == 32 || t_lo == 5) zsf = tr8(zss, zaddr + s * 32 * PZB, 4 * PZB);
             const int xb = xaddr + s * RS * 2 * PW * PXB;
 #pragma unroll
             for (int c = 0; c < NCT; ++c) {
@@ -274,7 +266,7 @@ __global__ __launch_bounds__(256) void wgrad7_kernel(const Wgrad7Params p) {
                     const int tap = t_lo + t;                // 9 = the shortcut: tap (1, 1)'s input fragment, the shortcut's gradient
                     const int tt = tap == 9 ? 4 : tap;
                     const int r = tt / 3, sx = tt - 3 * r;
-                    const uint4 xf = tr8_7(xs, xb + (r * PW + sx) * PXB + c * 32, 8 * PXB);
+                    const uint4 xf = tr8(xs, xb + (r * PW + sx) * PXB + c * 32, 8 * PXB);
                     acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, tap == 9 ? zsf : zf), __builtin_bit_cast(bf16x8_t, xf), acc[c][t], 0, 0, 0);
                 }
             }

@@ -4,7 +4,8 @@
 //     W_eff[q rows] = W[q rows] + sum_i c_i B_i A_i,   c_i = mag_i * inv_i   (inv_T = 1, inv_i = 1 / (|B_i|_F |A_i|_F) or 0 for i < T)
 // (v rows likewise, k rows untouched) that clhip_sdlora_refresh rewrites every step, and clhip_sdlora_grad produces the gradients of the
 // current term's A and B and of every magnitude from rank-sized products only -- no dense [D, D] weight gradient.  No atomics anywhere:
-// every sum over the M token rows is slab partials reduced in slab order, so two runs are bitwise equal.
+// every sum over the M token rows is slab partials (clhip_tn_slabs, tn_slab.hip: the routine the LoRA B gradient of vit_ops.hip uses) reduced
+// in slab order, so two runs are bitwise equal.
 // Factor table of one layer: 4 * nterms device pointers, [A_q terms | B_q terms | A_v terms | B_v terms]; A_i [r_i, D], B_i [D, r_i] fp32.
 #include <algorithm>
 
@@ -91,108 +92,6 @@ __global__ __launch_bounds__(256) void sdlora_pack_kernel(const float* const* __
         if (q < rT) v = f[(2 * which + 1) * nterms + nterms - 1][(size_t)c * rT + q];
         Elem<T>::st(bcat + (size_t)rb * D + c, v);
     }
-}
-
-// slab[s, w, o, j] = sum_{m in slab s} Y_w[m, o] Z_w[m, j]  (the K = M products), Y_w = Y + w * ystep (row pitch ldy), Z_w = Z + w * zstep (row pitch
-// ldz), o < O, j < J (J % 16 == 0).  Plain FMA: one thread per o, 16 columns j per workgroup -- the fp32 parity mode.
-template <typename T>
-__global__ __launch_bounds__(256) void sdlora_tn_kernel(const T* __restrict__ Y, int ldy, int ystep, const T* __restrict__ Z, int ldz, int zstep,
-                                                         float* __restrict__ slab, int M, int O, int J, int nw, int rows_per_slab) {
-    __shared__ float ps[64][16];
-    const int jt = blockIdx.z % (J / 16), w = blockIdx.z / (J / 16);
-    Y += (size_t)w * ystep;
-    Z += (size_t)w * zstep + jt * 16;
-    const int o = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-    const int m0 = s * rows_per_slab, m1 = min(M, m0 + rows_per_slab);
-    float acc[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    for (int mb = m0; mb < m1; mb += 64) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 64 * 16; i += 256) {
-            const int r = i >> 4, q = i & 15;
-            ps[r][q] = (mb + r) < m1 ? Elem<T>::ld(Z + (size_t)(mb + r) * ldz + q) : 0.f;
-        }
-        __syncthreads();
-        if (o < O) {
-            const int nr = min(64, m1 - mb);
-            for (int r = 0; r < nr; ++r) {
-                const float dy = Elem<T>::ld(Y + (size_t)(mb + r) * ldy + o);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[q] += dy * ps[r][q];
-            }
-        }
-    }
-    if (o < O) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) slab[(((size_t)s * nw + w) * O + o) * J + jt * 16 + q] = acc[q];
-    }
-}
-
-// the same product on the bf16 MFMA (O % 64 == 0, J % 32 == 0): lora_db_mfma_kernel's scheme (vit_ops.hip) with general operands.  Both operands are
-// read with the transposing LDS read from row-major tiles (rows = m), 32 rows per step, k-slot j of lane group g <-> row 4 g + (j & 3) + 16 (j >> 2)
-// on BOTH operands.  Workgroup = 64 columns o x 32 columns j; wave w owns o in [16 w, 16 w + 16).
-constexpr int YP = 160, PP = 96;      // LDS pitches (bytes) of the Y tile rows (64 bf16) and the Z tile rows (32 bf16)
-
-__device__ __forceinline__ uint4 tr8(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-
-__global__ __launch_bounds__(256) void sdlora_tn_mfma_kernel(const bf16_t* __restrict__ Y, int ldy, int ystep, const bf16_t* __restrict__ Z, int ldz, int zstep,
-                                                              float* __restrict__ slab, int M, int O, int J, int nw, int rows_per_slab) {
-    __shared__ __attribute__((aligned(16))) char ys[2][32 * YP];
-    __shared__ __attribute__((aligned(16))) char ps[2][32 * PP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
-    const int jt = blockIdx.z % (J / 32), w = blockIdx.z / (J / 32);
-    const int o0 = blockIdx.x * 64;
-    const int m0 = blockIdx.y * rows_per_slab, m1 = min(M, m0 + rows_per_slab);
-    const int yr = tid >> 3, yc = tid & 7;                          // Y tile: 32 rows x 8 chunks
-    const int pr = tid >> 2, pc = tid & 3;                          // Z tile: 32 rows x 4 chunks (threads < 128)
-    const bf16_t* ysrc = Y + (size_t)w * ystep + o0 + yc * 8;
-    const bf16_t* zsrc = Z + (size_t)w * zstep + jt * 32 + pc * 8;
-    uint4 ry, rp;
-    auto gload = [&](int mb) {
-        const int my = mb + yr, mp = mb + pr;
-        ry = my < m1 ? *reinterpret_cast<const uint4*>(ysrc + (size_t)my * ldy) : make_uint4(0, 0, 0, 0);
-        if (tid < 128) rp = mp < m1 ? *reinterpret_cast<const uint4*>(zsrc + (size_t)mp * ldz) : make_uint4(0, 0, 0, 0);
-    };
-    auto sstore = [&](int st) {
-        *reinterpret_cast<uint4*>(ys[st] + yr * YP + yc * 16) = ry;
-        if (tid < 128) *reinterpret_cast<uint4*>(ps[st] + pr * PP + pc * 16) = rp;
-    };
-    const int ya = (g * 4 + (l15 >> 2)) * YP + (wave * 16 + (l15 & 3) * 4) * 2;
-    const int pa = (g * 4 + (l15 >> 2)) * PP + (l15 & 3) * 8;
-    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-    if (m0 < m1) {
-        gload(m0);
-        sstore(0);
-        __syncthreads();
-        int st = 0;
-        for (int mb = m0; mb < m1; mb += 32, st ^= 1) {
-            const bool more = mb + 32 < m1;
-            if (more) gload(mb + 32);
-            const uint4 a = tr8(ys[st], ya, 16 * YP);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const uint4 b = tr8(ps[st], pa + t * 32, 16 * PP);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[t], 0, 0, 0);
-            }
-            if (more) sstore(st ^ 1);
-            __syncthreads();
-        }
-    }
-    // D[row = o (4 g + e)][col = j (l15 + 16 t)]
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int o = o0 + wave * 16 + g * 4 + e;
-            slab[(((size_t)blockIdx.y * nw + w) * O + o) * J + jt * 32 + l15 + 16 * t] = acc[t][e];
-        }
 }
 
 // slabs in slab order -> S [2, D, Rp] (kept for the magnitude gradients), dB_T = m_T S_T and dA_T = m_T (U^T X) of q and v, all WRITTEN
@@ -321,17 +220,9 @@ extern "C" int clhip_sdlora_grad(const void* x, const void* dqkv, const float* c
     if (int rc = clhip_gemm_nt(dq, bcat, U, nullptr, nullptr, nullptr, M, 16, D, 3 * D, D, 32, 0, 0, 0, dtype, stream)) return rc;
     if (int rc = clhip_gemm_nt(dq + (size_t)2 * D * e, bcat + (size_t)16 * D * e, U + 16 * e, nullptr, nullptr, nullptr, M, 16, D, 3 * D, D, 32, 0, 0, 0, dtype, stream))
         return rc;
-    // K = M: S_w = dY_w^T P_w [D, Rp] (w = q, v) and [dA_q^T | dA_v^T] = X^T U [D, 32]
-    if (dtype == CLHIP_BF16) {
-        hipLaunchKernelGGL(sdlora_tn_mfma_kernel, dim3(D / 64, nslab, 2 * (Rp / 32)), dim3(256), 0, s, (const bf16_t*)dqkv, 3 * D, 2 * D, (const bf16_t*)P, 2 * Rp, Rp,
-                           slabS, M, D, Rp, 2, rows);
-        hipLaunchKernelGGL(sdlora_tn_mfma_kernel, dim3(D / 64, nslab, 1), dim3(256), 0, s, (const bf16_t*)x, D, 0, (const bf16_t*)U, 32, 0, slabA, M, D, 32, 1, rows);
-    } else {
-        hipLaunchKernelGGL(sdlora_tn_kernel<float>, dim3((D + 255) / 256, nslab, 2 * (Rp / 16)), dim3(256), 0, s, (const float*)dqkv, 3 * D, 2 * D, (const float*)P,
-                           2 * Rp, Rp, slabS, M, D, Rp, 2, rows);
-        hipLaunchKernelGGL(sdlora_tn_kernel<float>, dim3((D + 255) / 256, nslab, 2), dim3(256), 0, s, (const float*)x, D, 0, (const float*)U, 32, 0, slabA, M, D, 32,
-                           1, rows);
-    }
+    // K = M (tn_slab.hip): S_w = dY_w^T P_w [D, Rp] (w = q, v) and [dA_q^T | dA_v^T] = X^T U [D, 32]; MFMA in bf16, plain FMA in fp32
+    if (int rc = clhip_tn_slabs(dqkv, dtype, 3 * D, 2 * D, P, dtype, 2 * Rp, Rp, 0, slabS, M, D, Rp, 2, rows, s)) return rc;
+    if (int rc = clhip_tn_slabs(x, dtype, D, 0, U, dtype, 32, 0, 0, slabA, M, D, 32, 1, rows, s)) return rc;
     const size_t nred = (size_t)2 * D * Rp + (size_t)D * 32;
     hipLaunchKernelGGL(sdlora_reduce_kernel, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, s, slabS, slabA, nslab, D, Rp, offT, rT, mag, nterms, S, d_a_q, d_b_q,
                        d_a_v, d_b_v);

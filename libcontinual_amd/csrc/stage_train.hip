@@ -452,14 +452,6 @@ struct StGeoB {
     static constexpr int LDS = GRP ? G::BUF + AUX + StGrp<C, HW>::BYTES : 2 * G::BUF + AUX + (C == 16 ? 4 * 2304 * 4 + HW * HW * 32 : 0);      // (16 channels: + the residual gradient of the block in flight, parked in LDS)
 };
 
-__device__ __forceinline__ uint4 st_tr8(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-
 // dw[k][tap][c] of ONE 16-channel image (stage 1): A = dz^T (rows = output channels, reduction = 32 pixels = one image row), B = the input image shifted by the tap,
 // both fetched from the pixel-major padded LDS images with transposing reads (ds_read_b64_tr_b16: 16 lanes fetch a [4 pixels][16 channels] block, lane i keeps
 // channel i).  The reduction index is a free permutation as long as both operands use the same one: lane group fg takes pixels 4 fg .. 4 fg + 3 and 16 + 4 fg .. of
@@ -482,9 +474,9 @@ __device__ __forceinline__ void st_wgrad16(const char* D, const char* XA, float*
     auto xrow = [&](int j, int slot) {                              // image row row0 + j = padded row row0 + j + 1 (rows -1 and HW are the zero halo)
         const int pb = ((row0 + j + 1) * P + col + 1) * PB + seg;
 #pragma unroll
-        for (int sx = 0; sx < 3; ++sx) X[slot][sx] = st_tr8(XA, pb + (sx - 1) * PB, 16 * PB);
+        for (int sx = 0; sx < 3; ++sx) X[slot][sx] = tr8(XA, pb + (sx - 1) * PB, 16 * PB);
     };
-    auto zrow = [&](int j, int b) { zf[b] = st_tr8(D, ((row0 + j + 1) * P + col + 1) * PB + seg, 16 * PB); };
+    auto zrow = [&](int j, int b) { zf[b] = tr8(D, ((row0 + j + 1) * P + col + 1) * PB + seg, 16 * PB); };
     xrow(-1, 0); xrow(0, 1); xrow(1, 2);
     zrow(0, 0);
 #pragma unroll
@@ -529,12 +521,12 @@ __device__ __forceinline__ void st_wgrad_wide(const char* D, const char* XA, flo
             const int pb = ((h0 + prow + 1) * P + pcol + 1) * PB + seg;
             uint4 zf[2];
 #pragma unroll
-            for (int o = 0; o < 2; ++o) zf[o] = st_tr8(D, pb + o * 32, 4 * PB);
+            for (int o = 0; o < 2; ++o) zf[o] = tr8(D, pb + o * 32, 4 * PB);
 #pragma unroll
             for (int q = 0; q < 5; ++q) {
                 if (q < nt) {
                     const int t = t0 + q, r = t / 3, sx = t - 3 * r;
-                    const uint4 xf = st_tr8(XA, pb + ((r - 1) * P + (sx - 1)) * PB + it * 32, 4 * PB);
+                    const uint4 xf = tr8(XA, pb + ((r - 1) * P + (sx - 1)) * PB + it * 32, 4 * PB);
 #pragma unroll
                     for (int o = 0; o < 2; ++o)
                         acc[o][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zf[o]), __builtin_bit_cast(bf16x8_t, xf), acc[o][q], 0, 0, 0);
@@ -562,11 +554,11 @@ __device__ __forceinline__ void st_wgrad_wide(const char* D, const char* XA, flo
                 const int pb = ((h0 + prow + 1) * P + pcol + 1) * PB + seg;
                 uint4 zf[2];
 #pragma unroll
-                for (int o = 0; o < 2; ++o) zf[o] = st_tr8(D, pb + (op * 2 + o) * 32, 4 * PB);
+                for (int o = 0; o < 2; ++o) zf[o] = tr8(D, pb + (op * 2 + o) * 32, 4 * PB);
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
                     const int r = t / 3, sx = t - 3 * r;
-                    const uint4 xf = st_tr8(XA, pb + ((r - 1) * P + (sx - 1)) * PB + it * 32, 4 * PB);
+                    const uint4 xf = tr8(XA, pb + ((r - 1) * P + (sx - 1)) * PB + it * 32, 4 * PB);
 #pragma unroll
                     for (int o = 0; o < 2; ++o)
                         acc[o][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zf[o]), __builtin_bit_cast(bf16x8_t, xf), acc[o][t], 0, 0, 0);
@@ -664,10 +656,10 @@ __device__ __forceinline__ void st_grp_run(const StGrpRegs<C, HW>& r, char* stg,
         const int j = ks / Q::KPI, ls = ks - j * Q::KPI;
         const char* xs = stg + j * Q::IMG;
         const int row = ls * RSTEP + row0;
-        zf[b] = st_tr8(xs + Q::XS, (row * HW + col0) * 32 + seg, SECOND * HW * 32);
+        zf[b] = tr8(xs + Q::XS, (row * HW + col0) * 32 + seg, SECOND * HW * 32);
         const int xb = ((row + 1) * P2 + col0 + 1) * 32 + seg;
 #pragma unroll
-        for (int q = 0; q < 5; ++q) xf[b][q] = st_tr8(xs, xb + toff[q], SECOND * P2 * 32);
+        for (int q = 0; q < 5; ++q) xf[b][q] = tr8(xs, xb + toff[q], SECOND * P2 * 32);
     };
     fetch(0, 0);
 #pragma unroll
@@ -726,17 +718,17 @@ __device__ __forceinline__ void st_wgrad_entry(const char* D, const char* Dds, c
         for (int h0 = 0; h0 < HW; h0 += 2) {
             const int pd = ((h0 + prow + 1) * P + pcol + 1) * PB + ot * 32 + seg;
             const int pi = (2 * (h0 + prow) * PI + 2 * pcol) * PBI + seg;
-            const uint4 zf = st_tr8(D, pd, 4 * PB);
+            const uint4 zf = tr8(D, pd, 4 * PB);
 #pragma unroll
             for (int q = 0; q < 5; ++q)
                 if (q < nt) {
                     const int t = t0 + q, dy = t / 3, dx = t - 3 * dy;
-                    const uint4 xf = st_tr8(IN, pi + (dy * PI + dx) * PBI, 8 * PBI);
+                    const uint4 xf = tr8(IN, pi + (dy * PI + dx) * PBI, 8 * PBI);
                     acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zf), __builtin_bit_cast(bf16x8_t, xf), acc[q], 0, 0, 0);
                 }
             if (th == 0) {                                          // (the shortcut's weight gradient rides on the tap-half-0 waves)
-                const uint4 zd = st_tr8(Dds, pd, 4 * PB);
-                const uint4 xf = st_tr8(IN, pi + (PI + 1) * PBI, 8 * PBI);
+                const uint4 zd = tr8(Dds, pd, 4 * PB);
+                const uint4 xf = tr8(IN, pi + (PI + 1) * PBI, 8 * PBI);
                 accd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zd), __builtin_bit_cast(bf16x8_t, xf), accd, 0, 0, 0);
             }
         }
@@ -763,13 +755,13 @@ __device__ __forceinline__ void st_wgrad_entry(const char* D, const char* Dds, c
         for (int h0 = 0; h0 < HW; h0 += 4) {
             const int pd = ((h0 + prow + 1) * P + pcol + 1) * PB + ot * 32 + seg;
             const int pi = (2 * (h0 + prow) * PI + 2 * pcol) * PBI + seg;
-            const uint4 zf = st_tr8(D, pd, 4 * PB), zd = st_tr8(Dds, pd, 4 * PB);
+            const uint4 zf = tr8(D, pd, 4 * PB), zd = tr8(Dds, pd, 4 * PB);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
                     const int dy = t / 3, dx = t - 3 * dy;
-                    const uint4 xf = st_tr8(IN, pi + (dy * PI + dx) * PBI + i * 32, 8 * PBI);
+                    const uint4 xf = tr8(IN, pi + (dy * PI + dx) * PBI + i * 32, 8 * PBI);
                     acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zf), __builtin_bit_cast(bf16x8_t, xf), acc[i][t], 0, 0, 0);
                     if (t == 4) accd[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, zd), __builtin_bit_cast(bf16x8_t, xf), accd[i], 0, 0, 0);
                 }

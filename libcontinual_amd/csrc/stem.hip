@@ -109,14 +109,6 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const StemParams p) {
 // gradient of the ResNets.
 struct StemWParams { const bf16_t* x; const bf16_t* dz; float* slab; int N, H, W, K, M, Creal, nstep; };
 
-__device__ __forceinline__ bf16x8_t tr8s(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return __builtin_bit_cast(bf16x8_t, make_uint4(l.x, l.y, h.x, h.y));
-}
-
 template <int KT>
 __global__ __launch_bounds__(256) void wgrad_stem_kernel(const StemWParams p) {
     constexpr int PZ = KT * 32 + 16, PX = 176;               // LDS pitches: gradient row (16 KT channels), im2col row (10 x 16 B + pad)
@@ -177,9 +169,9 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(const StemWParams p) {
         if (s + nw < p.nstep) fetch(s + nw);
         bf16x8_t zf[KT], xf[5];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) zf[kt] = tr8s(zs, col * PZ + kt * 32 + seg, 4 * PZ);
+        for (int kt = 0; kt < KT; ++kt) zf[kt] = tr8b(zs, col * PZ + kt * 32 + seg, 4 * PZ);
 #pragma unroll
-        for (int j = 0; j < 5; ++j) xf[j] = tr8s(xs, col * PX + j * 32 + seg, 4 * PX);
+        for (int j = 0; j < 5; ++j) xf[j] = tr8b(xs, col * PX + j * 32 + seg, 4 * PX);
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll

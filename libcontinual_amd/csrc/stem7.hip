@@ -161,14 +161,6 @@ __global__ __launch_bounds__(256) void conv_stem7_f32_kernel(const Stem7Params p
 // ------------------------------------------------------------------------------------------------------------ weight gradient
 struct Stem7WParams { const void* x; const void* dz; float* slab; int N, H, W, Ho, Wo, K, M, Creal, nstep; };
 
-__device__ __forceinline__ bf16x8_t tr8(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return __builtin_bit_cast(bf16x8_t, make_uint4(l.x, l.y, h.x, h.y));
-}
-
 // grid (splits, 7): workgroup (s, ky) accumulates dw[o][ky][kx][c] over the 32-pixel steps s * 4 + wave, + 4 splits, ...
 template <int KT>
 __global__ __launch_bounds__(256) void wgrad_stem7_kernel(const Stem7WParams p) {
@@ -228,9 +220,9 @@ __global__ __launch_bounds__(256) void wgrad_stem7_kernel(const Stem7WParams p) 
         if (s + nw < p.nstep) fetch(s + nw);
         bf16x8_t zf[KT], xf[4];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) zf[kt] = tr8(zs, col * PZ + kt * 32 + seg, 4 * PZ);
+        for (int kt = 0; kt < KT; ++kt) zf[kt] = tr8b(zs, col * PZ + kt * 32 + seg, 4 * PZ);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) xf[j] = tr8(xs, col * PX + j * 32 + seg, 4 * PX);
+        for (int j = 0; j < 4; ++j) xf[j] = tr8b(xs, col * PX + j * 32 + seg, 4 * PX);
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll

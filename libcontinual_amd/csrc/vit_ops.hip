@@ -326,111 +326,9 @@ __global__ __launch_bounds__(256) void lora_proj_kernel(const T* __restrict__ x,
         }
 }
 
-// slab[s, o, q] = sum_{m in slab s} dY[m, D + o] * P[m, (o >= D ? r : 0) + q]   (o in [0, 2D): dK columns then dV columns)
-template <typename T>
-__global__ __launch_bounds__(256) void lora_db_kernel(const T* __restrict__ dqkv, const float* __restrict__ P, float* __restrict__ slab, int M, int D,
-                                                       int rank, int rows_per_slab) {
-    __shared__ float ps[64][32];
-    const int o = blockIdx.x * 256 + threadIdx.x;                 // column of [dK | dV]
-    const int s = blockIdx.y;
-    const int m0 = s * rows_per_slab, m1 = min(M, m0 + rows_per_slab);
-    float acc[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    for (int mb = m0; mb < m1; mb += 64) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 64 * 2 * rank; i += 256) {
-            const int r = i / (2 * rank), q = i - r * 2 * rank;
-            ps[r][q] = (mb + r) < m1 ? P[(size_t)(mb + r) * 2 * rank + q] : 0.f;
-        }
-        __syncthreads();
-        if (o < 2 * D) {
-            const int po = (o >= D) ? rank : 0;
-            const int nr = min(64, m1 - mb);
-            for (int r = 0; r < nr; ++r) {
-                const float dy = Elem<T>::ld(dqkv + (size_t)(mb + r) * 3 * D + D + o);
-#pragma unroll
-                for (int q = 0; q < 16; ++q)
-                    if (q < rank) acc[q] += dy * ps[r][po + q];
-            }
-        }
-    }
-    if (o < 2 * D) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            if (q < rank) slab[((size_t)s * 2 * D + o) * rank + q] = acc[q];
-    }
-}
-
-// ---- bf16 fast path.  P16 [M, 32] = X . Acat^T comes from the MFMA GEMM (Acat = [A_k; A_v; 0] as a [32, D] bf16 matrix);
-// slab[s, o, q] = sum_m dY[m, D + o] P16[m, (o >= D ? r : 0) + q] is a "TN" product: both MFMA operands are read with the
-// transposing LDS read from row-major tiles (rows = m), 32 rows per step, k-slot j of lane group g <-> row g*4 + (j&3) + 16*(j>>2)
-// on BOTH operands (the slot order of an MFMA is free), which keeps the reads bank-conflict free at these pitches.
-constexpr int YP = 160, PP = 96;      // LDS pitches (bytes) of the dY tile rows (64 bf16) and the P tile rows (32 bf16)
-
-__device__ __forceinline__ uint4 tr8v(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, h.x, h.y);
-}
-
-__global__ __launch_bounds__(256) void lora_db_mfma_kernel(const bf16_t* __restrict__ dqkv, const bf16_t* __restrict__ P16, float* __restrict__ slab,
-                                                            int M, int D, int rank, int rows_per_slab) {
-    __shared__ __attribute__((aligned(16))) char ys[2][32 * YP];
-    __shared__ __attribute__((aligned(16))) char ps[2][32 * PP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
-    const int o0 = blockIdx.x * 64;                                 // column block of [dK | dV]
-    const int m0 = blockIdx.y * rows_per_slab, m1 = min(M, m0 + rows_per_slab);
-    const int qoff = o0 >= D ? rank : 0;                            // D % 64 == 0: a block never straddles dK / dV
-    const int yr = tid >> 3, yc = tid & 7;                          // dY tile: 32 rows x 8 chunks
-    const int pr = tid >> 2, pc = tid & 3;                          // P tile: 32 rows x 4 chunks (threads < 128)
-    const bf16_t* ysrc = dqkv + (size_t)D + o0 + yc * 8;
-    uint4 ry, rp;
-    auto gload = [&](int mb) {
-        const int my = mb + yr, mp = mb + pr;
-        ry = my < m1 ? *reinterpret_cast<const uint4*>(ysrc + (size_t)my * 3 * D) : make_uint4(0, 0, 0, 0);
-        if (tid < 128) rp = mp < m1 ? *reinterpret_cast<const uint4*>(P16 + (size_t)mp * 32 + pc * 8) : make_uint4(0, 0, 0, 0);
-    };
-    auto sstore = [&](int st) {
-        *reinterpret_cast<uint4*>(ys[st] + yr * YP + yc * 16) = ry;
-        if (tid < 128) *reinterpret_cast<uint4*>(ps[st] + pr * PP + pc * 16) = rp;
-    };
-    const int ya = (g * 4 + (l15 >> 2)) * YP + (wave * 16 + (l15 & 3) * 4) * 2;
-    const int pa = (g * 4 + (l15 >> 2)) * PP + (l15 & 3) * 8;
-    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-    if (m0 < m1) {
-        gload(m0);
-        sstore(0);
-        __syncthreads();
-        int st = 0;
-        for (int mb = m0; mb < m1; mb += 32, st ^= 1) {
-            const bool more = mb + 32 < m1;
-            if (more) gload(mb + 32);
-            const uint4 a = tr8v(ys[st], ya, 16 * YP);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const uint4 b = tr8v(ps[st], pa + t * 32, 16 * PP);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[t], 0, 0, 0);
-            }
-            if (more) sstore(st ^ 1);
-            __syncthreads();
-        }
-    }
-    // D[row = o (g*4+e)][col = q (l15 + 16 t)]; keep q in [qoff, qoff + rank)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int q = l15 + 16 * t - qoff;
-        if (q >= 0 && q < rank) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = o0 + wave * 16 + g * 4 + e;
-                slab[((size_t)blockIdx.y * 2 * D + o) * rank + q] = acc[t][e];
-            }
-        }
-    }
-}
+// The K = M product slab[s, o, q] = sum_{m in slab s} dY[m, D + o] * P[m, (o >= D ? r : 0) + q] (o in [0, 2D): dK columns then dV columns) is
+// clhip_tn_slabs (tn_slab.hip, shared with SD-LoRA) with two windows of r columns into the one P: plain FMA on the fp32 P above, or -- the bf16
+// fast path -- the MFMA form on P16 [M, 32] = X . Acat^T from the MFMA GEMM (Acat = [A_k; A_v; 0] as a [32, D] bf16 matrix).
 
 // Acat [32, D] (compute dtype) = rows [A_k (rank) ; A_v (rank) ; zeros]
 template <typename T>
@@ -500,7 +398,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const T* __restrict__ x, floa
 // bf16: G_l [D, D] += X_l^T X_l on the matrix cores, all layers of a pass in ONE launch (the Gram of every
 // attention input on the device, resident, instead of transformer.py:241-244's bmm + 2.4-MB transfer per layer and batch).  A "TN" product:
 // the reduction runs over the ROWS of X, so both MFMA operands come out of row-major LDS tiles through the transposing read (the
-// slot order of lora_db_mfma_kernel: k-slot j of lane group g <-> row 4 g + (j & 3) + 16 (j >> 2) on both operands).  Workgroup =
+// slot order of tn_slab_mfma_kernel: k-slot j of lane group g <-> row 4 g + (j & 3) + 16 (j >> 2) on both operands).  Workgroup =
 // one 128 x 128 tile of one layer over ALL rows (no row split: every element of G has one owner per launch, plain fp32 read-modify-
 // write, bitwise reproducible); 2 x 2 waves of 64 x 64 = 16 accumulator tiles each; 32 rows per step, register-staged, double-buffered.
 constexpr int GP = 544;               // LDS row pitch: 256 bf16 (the i panel, then the j panel) + 32 bytes -> rows 0..7 fall in disjoint 32-byte bank groups
@@ -550,9 +448,9 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const bf16_t* __restrict
         if (more) gload(mb + 32);
         uint4 af[4], bfr[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) af[a] = tr8v(xs[st], aa + a * 32, 16 * GP);
+        for (int a = 0; a < 4; ++a) af[a] = tr8(xs[st], aa + a * 32, 16 * GP);
 #pragma unroll
-        for (int b = 0; b < 4; ++b) bfr[b] = tr8v(xs[st], ba + b * 32, 16 * GP);
+        for (int b = 0; b < 4; ++b) bfr[b] = tr8(xs[st], ba + b * 32, 16 * GP);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -812,10 +710,12 @@ extern "C" int clhip_lora_merge(float* qkv_w, const float* lora_a_k, const float
     return CLHIP_OK;
 }
 
+// workspace of clhip_lora_grad: P (fp32 [M, 2r] or bf16 [M, 32], whichever is larger; this many bytes), then the slabs
+static size_t lora_p_bytes(int M, int rank) { return (std::max((size_t)M * 2 * rank * sizeof(float), (size_t)M * 32 * 2) + 255) / 256 * 256; }
+
 extern "C" size_t clhip_lora_grad_ws_bytes(int M, int D, int rank) {
     const int nslab = (M + 511) / 512;
-    const size_t p = std::max((size_t)M * 2 * rank * sizeof(float), (size_t)M * 32 * 2);
-    return (p + 255) / 256 * 256 + (size_t)nslab * 2 * D * rank * sizeof(float);
+    return lora_p_bytes(M, rank) + (size_t)nslab * 2 * D * rank * sizeof(float);
 }
 
 extern "C" int clhip_lora_acat(const float* lora_a_k, const float* lora_a_v, void* a_cat, int D, int rank, int dtype, void* stream) {
@@ -831,27 +731,20 @@ extern "C" int clhip_lora_grad(const void* x, const void* dqkv, const float* lor
                                void* ws, int M, int D, int rank, int dtype, void* stream) {
     CLHIP_CHECK_ARG(x && dqkv && lora_a_k && lora_a_v && d_b_k && d_b_v && ws && M > 0 && rank > 0 && rank <= 16);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == CLHIP_BF16 && a_cat != nullptr && D % 64 == 0) {
-        // MFMA path: P16 = X . Acat^T through the GEMM kernel, then the transposing-read TN product per 1024-row slab
-        const int rows = 1024, nslab = (M + rows - 1) / rows;
-        CLHIP_CHECK_ARG(nslab <= (M + 511) / 512);
-        bf16_t* P16 = static_cast<bf16_t*>(ws);
-        float* slab = reinterpret_cast<float*>(static_cast<char*>(ws) + (std::max((size_t)M * 2 * rank * sizeof(float), (size_t)M * 32 * 2) + 255) / 256 * 256);
-        if (int rc = clhip_gemm_nt(x, a_cat, P16, nullptr, nullptr, nullptr, M, 32, D, D, D, 32, 0, 0, 0, dtype, stream)) return rc;
-        hipLaunchKernelGGL(lora_db_mfma_kernel, dim3(2 * D / 64, nslab), dim3(256), 0, s, (const bf16_t*)dqkv, P16, slab, M, D, rank, rows);
-        hipLaunchKernelGGL(lora_db_reduce_kernel, dim3((2 * D * rank + 255) / 256), dim3(256), 0, s, slab, d_b_k, d_b_v, D, rank, nslab);
-        CLHIP_LAUNCH_CHECK();
-        return CLHIP_OK;
+    // MFMA path: P16 = X . Acat^T through the GEMM kernel, 1024-row slabs; else the fp32 P of lora_proj_kernel, 512-row slabs
+    const bool fast = dtype == CLHIP_BF16 && a_cat != nullptr && D % 64 == 0;
+    const int rows = fast ? 1024 : 512, nslab = (M + rows - 1) / rows;
+    float* slab = reinterpret_cast<float*>(static_cast<char*>(ws) + lora_p_bytes(M, rank));
+    if (fast) {
+        if (int rc = clhip_gemm_nt(x, a_cat, ws, nullptr, nullptr, nullptr, M, 32, D, D, D, 32, 0, 0, 0, dtype, stream)) return rc;
+    } else {
+        float* P = static_cast<float*>(ws);
+        DT_DISPATCH(dtype, hipLaunchKernelGGL(lora_proj_kernel<bf16_t>, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, lora_a_k, lora_a_v, P, M, D, rank),
+                    hipLaunchKernelGGL(lora_proj_kernel<float>, dim3((M + 3) / 4), dim3(256), 0, s, (const float*)x, lora_a_k, lora_a_v, P, M, D, rank));
     }
-    const int nslab = (M + 511) / 512;
-    float* P = static_cast<float*>(ws);
-    float* slab = reinterpret_cast<float*>(static_cast<char*>(ws) + (std::max((size_t)M * 2 * rank * sizeof(float), (size_t)M * 32 * 2) + 255) / 256 * 256);
-    dim3 g2((2 * D + 255) / 256, nslab);
-    DT_DISPATCH(dtype,
-                { hipLaunchKernelGGL(lora_proj_kernel<bf16_t>, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, lora_a_k, lora_a_v, P, M, D, rank);
-                  hipLaunchKernelGGL(lora_db_kernel<bf16_t>, g2, dim3(256), 0, s, (const bf16_t*)dqkv, P, slab, M, D, rank, 512); },
-                { hipLaunchKernelGGL(lora_proj_kernel<float>, dim3((M + 3) / 4), dim3(256), 0, s, (const float*)x, lora_a_k, lora_a_v, P, M, D, rank);
-                  hipLaunchKernelGGL(lora_db_kernel<float>, g2, dim3(256), 0, s, (const float*)dqkv, P, slab, M, D, rank, 512); });
+    // [dK | dV] = the 2 D columns from column D of dqkv; the k columns read P columns [0, r), the v columns [r, 2r)
+    const char* dkv = static_cast<const char*>(dqkv) + (size_t)D * (dtype == CLHIP_BF16 ? 2 : 4);
+    if (int rc = clhip_tn_slabs(dkv, dtype, 3 * D, D, ws, fast ? CLHIP_BF16 : CLHIP_F32, fast ? 32 : 2 * rank, 0, rank, slab, M, D, rank, 2, rows, s)) return rc;
     hipLaunchKernelGGL(lora_db_reduce_kernel, dim3((2 * D * rank + 255) / 256), dim3(256), 0, s, slab, d_b_k, d_b_v, D, rank, nslab);
     CLHIP_LAUNCH_CHECK();
     return CLHIP_OK;

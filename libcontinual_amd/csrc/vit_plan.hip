@@ -333,6 +333,16 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
         (void)hipEventCreateWithFlags(&v->ev_l, hipEventDisableTiming);
     }
     bool lora_pending = false;
+    // a leaf that reads dqkv: on the side stream once the caller's stream has written dqkv (ev_q), its end marked for the next writer (ev_l); else in line
+    auto leaf = [&](auto&& run) -> int {
+        if (!side_on) return run(stream);
+        (void)hipEventRecord(v->ev_q, main_s);
+        (void)hipStreamWaitEvent(v->side, v->ev_q, 0);
+        TRY(run(v->side));
+        (void)hipEventRecord(v->ev_l, v->side);
+        lora_pending = true;
+        return CLHIP_OK;
+    };
     TRY(clhip_ln_pool_bwd(dfeat, ws + L.x_in[d.depth], P->norm_w, g, B, N, D, L.P > 0 ? L.P : 1, 1e-6f, dt, stream));
     for (int l = d.depth - 1; l >= 0; --l) {
         const clhip_vit_layer_params& p = P->layers[l];
@@ -363,29 +373,19 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
                            reinterpret_cast<float*>(ws + L.dsum), B, N, d.heads, D, dt, stream));
         if (d_lora_b) {
             CLHIP_CHECK_ARG(p.lora_a_k && p.lora_a_v && d_lora_b[2 * l] && d_lora_b[2 * l + 1]);
-            void* ls = stream;
-            if (side_on) {
-                (void)hipEventRecord(v->ev_q, main_s);
-                (void)hipStreamWaitEvent(v->side, v->ev_q, 0);
-                ls = v->side;
-            }
-            TRY(clhip_lora_grad(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_a_v, sh + s.acat, d_lora_b[2 * l], d_lora_b[2 * l + 1], ws + L.lora_ws, M, D,
-                                d.lora_rank, dt, ls));
-            if (side_on) { (void)hipEventRecord(v->ev_l, v->side); lora_pending = true; }
+            TRY(leaf([&](void* ls) {
+                return clhip_lora_grad(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_a_v, sh + s.acat, d_lora_b[2 * l], d_lora_b[2 * l + 1], ws + L.lora_ws, M, D,
+                                       d.lora_rank, dt, ls);
+            }));
         }
         if (d_sd) {
             float* const* gs = d_sd + 4 * l;
             CLHIP_CHECK_ARG(gs[0] && gs[1] && gs[2] && gs[3]);
-            void* ls = stream;
-            if (side_on) {
-                (void)hipEventRecord(v->ev_q, main_s);
-                (void)hipStreamWaitEvent(v->side, v->ev_q, 0);
-                ls = v->side;
-            }
-            TRY(clhip_sdlora_grad(ws + L.h1[l], ws + L.dqkv, v->sd_factors + (size_t)l * 4 * v->sd_terms, v->sd_ranks.data(), v->sd_terms, v->sd_mag,
-                                  v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M, D,
-                                  dt, ls));
-            if (side_on) { (void)hipEventRecord(v->ev_l, v->side); lora_pending = true; }
+            TRY(leaf([&](void* ls) {
+                return clhip_sdlora_grad(ws + L.h1[l], ws + L.dqkv, v->sd_factors + (size_t)l * 4 * v->sd_terms, v->sd_ranks.data(), v->sd_terms, v->sd_mag,
+                                         v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M,
+                                         D, dt, ls);
+            }));
         }
         if (l == 0 && dprompt_tokens == nullptr) break;           // nothing below the first block needs a gradient
         TRY(clhip_gemm_nt(ws + L.dqkv, sh + s.qkv_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, 3 * D, 3 * D, 3 * D, D, 0, 0, EPI_NONE, dt, stream));

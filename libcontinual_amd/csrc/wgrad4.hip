@@ -81,15 +81,6 @@ __device__ __forceinline__ void wg_barrier4() {
     asm volatile("" ::: "memory");
 }
 
-// two transposing 8-byte reads -> the 8 reduction elements (pixels) of one MFMA operand row; `second` = byte distance of pixels k+4..k+7
-__device__ __forceinline__ bf16x8_t tr8x(const char* base, int addr, int second) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + addr + second));
-    uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
-    return __builtin_bit_cast(bf16x8_t, make_uint4(l.x, l.y, h.x, h.y));
-}
-
 // The LDS-DMA is issued from inline asm ON PURPOSE.  hipcc (ROCm 7.2) knows that a `buffer_load ... lds` builtin writes LDS and puts
 // `s_waitcnt vmcnt(0)` in front of the first ds_read_tr intrinsic that follows one (the intrinsic carries an LDS memory operand which
 // every DMA in flight may alias) -- the ring would be drained every step.  Hidden in asm, the DMA is invisible to that bookkeeping;
@@ -244,11 +235,11 @@ __global__ __launch_bounds__(512) void conv_wgrad4_kernel(const Wgrad4Params p) 
         for (int u = 0; u < UK; ++u) {
             bf16x8_t zf[4];
 #pragma unroll
-            for (int oi = 0; oi < 4; ++oi) zf[oi] = tr8x(sb, zaddr[u] + oi * 32, 4 * P4);
+            for (int oi = 0; oi < 4; ++oi) zf[oi] = tr8b(sb, zaddr[u] + oi * 32, 4 * P4);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int r = t / 3, s2 = t - 3 * r;
-                const bf16x8_t xf = tr8x(sb, xaddr[u] + (r * PW + s2) * P4, xsecond);
+                const bf16x8_t xf = tr8b(sb, xaddr[u] + (r * PW + s2) * P4, xsecond);
 #pragma unroll
                 for (int oi = 0; oi < 4; ++oi) acc[oi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, zf[oi], acc[oi][t], 0, 0, 0);
             }

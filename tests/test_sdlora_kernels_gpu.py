@@ -23,6 +23,10 @@ DT = {"f32": (_lib.F32, torch.float32, 0.0), "bf16": (_lib.BF16, torch.bfloat16,
 RANKS = {"r10": [10], "r10x2": [10, 10], "r10_8_6_6": [10, 8, 6, 6], "r16x3": [16, 16, 16]}
 SHAPES = [(D, M, k) for D in (64, 128) for M in (1, 65, 591) for k in RANKS] + [(768, 394, "r10x3"), (64, 1100, "r10x2")]       # the last: two slabs of rows
 RANKS["r10x3"] = [10, 10, 10]
+RANKS["r1"] = [1]
+# the shared slab product (csrc/tn_slab.hip): one row short of, on and one row past the 1024-row slab edge, and the first M that sizes its slabs by the
+# second rule (ceil(ceil(M / 16) / 64) * 64 = 1088 rows, 16 slabs)
+SHAPES += [(64, M, k) for M in (1023, 1024, 1025) for k in ("r1", "r10x2")] + [(64, 16385, "r10x2")]
 
 
 def _st():
