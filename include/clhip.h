@@ -392,11 +392,26 @@ int clhip_herding_select_batched(const float* feats, const int32_t* offsets, int
  *   255,1267-1271) and, with the [in,out] copy of a frozen weight as B, its input gradient.  Epilogues:
  *   0 none | 1 +bias | 2 +bias +R (residual add, :1333-1334) | 3 +bias, then C <- GELU(.) (:1268) and H <- GELU'(.)
  *   (nullable; saved for the backward) | 4 C <- (.) * H (backward of 3).  bias fp32; R, H in the compute dtype.
- *   K % 64 == 0, N % 4 == 0.  Products with fewer than 256 tiles of 128 x 128 and K >= 3072 (bf16) run as 2-4 K slices + one fixed-order
+ *   K % 64 == 0, N % 4 == 0, lda and ldb % 8 == 0.  Output-side pitches (ldc; ldr when R is given; ldh when H is given): % 4 == 0, and % 8 == 0 for a
+ *   bf16 product with N % 8 == 0 -- its kernels move C, R and H as 16-byte chunks at row * ld + 8 c, so every row must start 16-byte aligned (bf16 with
+ *   N % 8 == 4 stores 8 bytes at a time and fp32 rows of ld % 4 == 0 are 16-byte aligned: both keep % 4).  Anything else is CLHIP_EINVAL before a launch.
+ *   Products with fewer than 256 tiles of 128 x 128 and K >= 3072 (bf16) run as 2-4 K slices + one fixed-order
  *   reduce / epilogue pass through a library-owned fp32 scratch (per stream, allocated at the first such call outside stream capture, never
  *   freed while a graph may hold it); results are bitwise reproducible either way.                                                          */
 int clhip_gemm_nt(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
                   int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, int dtype, void* stream);
+/* The launches clhip_gemm_nt would make for this call, in order (host code only, no device needed): launches[4 i .. 4 i + 3] = kernel family
+ * (below), first row, row count, K slices (> 1: split-K, the 128 x 128 tile per slice + the reduce / epilogue pass) for i < min(return value,
+ * max_launches).  Returns the number of launches (at most 3: gemm8 rows, one 256 x 256 head, the small-tile rest) or CLHIP_EINVAL for a shape or
+ * pitch clhip_gemm_nt rejects (the same check; ldr and ldh are judged as in a call that gives R and H, so pass 0 or N for an absent one).  clhip_gemm_nt switches on the same decision; the current clhip_gemm8_config mode and CLHIP_GEMM_* switches apply.  A split-K
+ * launch is the intent: a call that finds no scratch (stream capture) runs those rows unsplit. */
+#define CLHIP_GEMM_GEMM8 1    /* gemm8.hip, 256 x 256 persistent */
+#define CLHIP_GEMM_256 2      /* register-staged 256 x 256, 8 waves */
+#define CLHIP_GEMM_160 3      /* 160 x 128 */
+#define CLHIP_GEMM_128 4      /* 128 x 128 */
+#define CLHIP_GEMM_64 5       /* 64 x 64 */
+#define CLHIP_GEMM_F32_128 6  /* fp32 parity mode, 128 x 128 */
+int clhip_gemm_nt_route(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype, int* launches, int max_launches);
 /* The input gradient AND the weight gradient of one layer in ONE launch (both consume dz and nothing of each other): the layers whose two
  * backward convolutions are launches at their latency floor -- 3x3/s1/p1 with 16 -> 16 channels on 32-wide or 32 -> 32 channels on 16-wide
  * images, bf16 (CifarResNet-32 stages 1 and 2, core/model/backbone/resnet.py:289-316 under autograd).  Same arguments and results (bit for

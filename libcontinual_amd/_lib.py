@@ -160,6 +160,7 @@ _PROTOS = {
     "clhip_augment_rrc_aa_ws_bytes": (_sz, [_i, _i, _i]),
     "clhip_augment_rrc_aa": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),
     "clhip_gemm_nt": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 10 + [_p]),
+    "clhip_gemm_nt_route": (_i, [_i] * 9 + [C.POINTER(C.c_int), _i]),
     "clhip_config": (_i, [C.c_char_p, C.c_char_p]),
     "clhip_config_get": (C.c_char_p, [C.c_char_p]),
     "clhip_conv_bn_input_wt_supported": (_i, [_i] * 9),

@@ -18,6 +18,11 @@
 
 #include "common.h"
 
+// gemm8.hip
+int clhip_gemm8_rows(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype);
+int clhip_gemm8_launch(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
+                       int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, hipStream_t st);
+
 namespace {
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4 };
@@ -483,132 +488,180 @@ int pick_tile(int M, int N) {
     return best;
 }
 
-template <typename T, int EPI> int launch_mt(const GemmParams& p, hipStream_t s, bool allow_split = true) {
-    if constexpr (sizeof(T) == 4) {
-        return launch<T, EPI, 4, 4>(p, s);
-    } else {
-        // Narrow outputs with a long K (the ViT's N = 768 GEMMs, 36 % of an InfLoRA step): 256 x 256 tiles are 30 % faster per
-        // tile (891 vs 647 TFLOP/s at K = 3072) but 297 of them on 256 CUs take two rounds.  Run exactly one round of 256 x 256
-        // tiles on the leading rows and hand the remaining rows to the small-tile kernels (a second, short launch).
-        static const bool no_split = clhip_cfg("GEMM_NO_SPLIT") != nullptr || clhip_cfg("GEMM_MT") != nullptr;
-        // Few output tiles, long K (L2P at batch 16: [3552 x 3072] . [768 x 3072]^T is 168 tiles of 128 x 128 -- the 64 x 64 tiles that filled the chip instead ran
-        // at 422 TFLOP/s against the vendor's 693): 128 x 128 tiles over 2-4 K slices, then one reduce + epilogue pass (profiles/r04_gemm_vs_blas.txt).
-        // Measured (r04_gemm_vs_blas.txt, M = 3552, N = 768): K = 3072 39.7 -> 35.4 us (vendor 24.9), K = 2304 25.4 -> 29.4 us -- the slices' 128 x 128 tiles run at the same
-        // ~600 TFLOP/s as the rest of this kernel and the second pass costs ~7 us, so only the longest K gains; CLHIP_GEMM_SPLITK = 0 disables, any other value = the minimum K.
-        static const bool no_splitk = clhip_cfg("GEMM_SPLITK") != nullptr && atoi(clhip_cfg("GEMM_SPLITK")) == 0;
-        static const int splitk_min_k = (clhip_cfg("GEMM_SPLITK") != nullptr && atoi(clhip_cfg("GEMM_SPLITK")) > 1) ? atoi(clhip_cfg("GEMM_SPLITK")) : 3072;
-        if (allow_split && !no_split && !no_splitk && p.ksplit == 1 && p.K >= splitk_min_k && (p.N & 3) == 0) {
-            const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-            if (t128 < 256) {
-                const int ksteps = p.K / BK;
-                int ks = (int)(512 / t128);
-                if (ks > 4) ks = 4;
-                while (ks > 1 && (ksteps % ks != 0 || ksteps / ks < 8)) --ks;
-                if (ks > 1) {
-                    float* ws = splitk_scratch(s, (size_t)ks * p.M * p.N * sizeof(float));
-                    if (ws != nullptr) {
-                        GemmParams q = p;
-                        q.ksplit = ks; q.part = ws + 1024; q.group_m = 1;
-                        // (round 5 also had the LAST slice of a tile reduce and store it -- one launch instead of two; measured slower, [3552 x 768 x 3072] 34.7 -> 54.7 us:
-                        //  three 64-KB slices per tile read behind agent-scope fences cost the reducer more than the second launch does; removed in round 6)
-                        return launch<T, EPI, 4, 4>(q, s);
-                    }
-                }
-            }
+// ONE decision for clhip_gemm_nt and clhip_gemm_nt_route: which kernels run which rows.  A launch = (kernel family, first row, rows, K slices).
+struct Launch { int kind, row0, rows, ks; };
+struct Route {
+    static constexpr int MAX = 3;                             // gemm8 rows, a 256 x 256 head, the small-tile rest
+    int n = 0;
+    bool overflow = false;                                    // a launch that did not fit: the callers fail instead of leaving its rows unwritten
+    Launch l[MAX];
+    void add(int kind, int row0, int rows, int ks) { if (n < MAX) l[n++] = Launch{kind, row0, rows, ks}; else overflow = true; }
+};
+
+// the register-staged kernels on rows [row0, row0 + M)
+void route_mt(Route& r, int row0, int M, int N, int K, bool f32, bool allow_split, bool allow_splitk) {
+    if (f32) { r.add(CLHIP_GEMM_F32_128, row0, M, 1); return; }
+    // Narrow outputs with a long K (the ViT's N = 768 GEMMs, 36 % of an InfLoRA step): 256 x 256 tiles are 30 % faster per
+    // tile (891 vs 647 TFLOP/s at K = 3072) but 297 of them on 256 CUs take two rounds.  Run exactly one round of 256 x 256
+    // tiles on the leading rows and hand the remaining rows to the small-tile kernels (a second, short launch).
+    static const bool no_split = clhip_cfg("GEMM_NO_SPLIT") != nullptr || clhip_cfg("GEMM_MT") != nullptr;
+    // Few output tiles, long K (L2P at batch 16: [3552 x 3072] . [768 x 3072]^T is 168 tiles of 128 x 128 -- the 64 x 64 tiles that filled the chip instead ran
+    // at 422 TFLOP/s against the vendor's 693): 128 x 128 tiles over 2-4 K slices, then one reduce + epilogue pass (profiles/r04_gemm_vs_blas.txt).
+    // Measured (r04_gemm_vs_blas.txt, M = 3552, N = 768): K = 3072 39.7 -> 35.4 us (vendor 24.9), K = 2304 25.4 -> 29.4 us -- the slices' 128 x 128 tiles run at the same
+    // ~600 TFLOP/s as the rest of this kernel and the second pass costs ~7 us, so only the longest K gains; CLHIP_GEMM_SPLITK = 0 disables, any other value = the minimum K.
+    static const bool no_splitk = clhip_cfg("GEMM_SPLITK") != nullptr && atoi(clhip_cfg("GEMM_SPLITK")) == 0;
+    static const int splitk_min_k = (clhip_cfg("GEMM_SPLITK") != nullptr && atoi(clhip_cfg("GEMM_SPLITK")) > 1) ? atoi(clhip_cfg("GEMM_SPLITK")) : 3072;
+    if (allow_split && allow_splitk && !no_split && !no_splitk && K >= splitk_min_k && (N & 3) == 0) {
+        const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+        if (t128 < 256) {
+            const int ksteps = K / BK;
+            int ks = (int)(512 / t128);
+            if (ks > 4) ks = 4;
+            while (ks > 1 && (ksteps % ks != 0 || ksteps / ks < 8)) --ks;
+            // (round 5 also had the LAST slice of a tile reduce and store it -- one launch instead of two; measured slower, [3552 x 768 x 3072] 34.7 -> 54.7 us:
+            //  three 64-KB slices per tile read behind agent-scope fences cost the reducer more than the second launch does; removed in round 6)
+            if (ks > 1) { r.add(CLHIP_GEMM_128, row0, M, ks); return; }
         }
-        if (allow_split && !no_split && p.N % 256 == 0 && p.K >= 2304) {
-            const int tn = p.N / 256;
-            const long t256 = (long)((p.M + 255) / 256) * tn;
-            const int head_rows = (256 / tn) * 256;
-            if (tn <= 4 && t256 > 256 && t256 < 448 && head_rows < p.M) {
-                GemmParams h = p, t = p;
-                h.M = head_rows;
-                if (int rc = launch<T, EPI, 8, 4, 2, 4>(h, s)) return rc;
-                const size_t es = sizeof(T);
-                t.M = p.M - head_rows;
-                t.A = static_cast<const char*>(p.A) + (size_t)head_rows * p.lda * es;
-                t.C = static_cast<char*>(p.C) + (size_t)head_rows * p.ldc * es;
-                if (p.R) t.R = static_cast<const char*>(p.R) + (size_t)head_rows * p.ldr * es;
-                if (p.H) t.H = static_cast<char*>(p.H) + (size_t)head_rows * p.ldh * es;
-                return launch_mt<T, EPI>(t, s, false);
-            }
+    }
+    if (allow_split && !no_split && N % 256 == 0 && K >= 2304) {
+        const int tn = N / 256;
+        const long t256 = (long)((M + 255) / 256) * tn;
+        const int head_rows = (256 / tn) * 256;
+        if (tn <= 4 && t256 > 256 && t256 < 448 && head_rows < M) {
+            r.add(CLHIP_GEMM_256, row0, head_rows, 1);
+            route_mt(r, row0 + head_rows, M - head_rows, N, K, f32, false, false);
+            return;
         }
-        // short K, wide N (qkv / fc1 / the fc2 activation gradient, K = 768): the last of the 3.5 - 4.6 rounds of 256 x 256 tiles is
-        // poorly filled.  Whole rounds of big tiles run on the leading rows, the remaining rows on the small tiles (qkv forward
-        // 151.7 -> 139.0 us; CLHIP_GEMM_TAIL=0 disables).  Only when the last round is < 160 of 256 tiles: a fuller one costs more as small tiles.
-        static const bool tail_split = !(clhip_cfg("GEMM_TAIL") != nullptr && atoi(clhip_cfg("GEMM_TAIL")) == 0);
-        if (allow_split && tail_split && !no_split && p.N % 256 == 0 && pick_tile(p.M, p.N) == 8) {
-            const int tn = p.N / 256;
-            const long t256 = (long)((p.M + 255) / 256) * tn;
-            const long full = t256 / 256;
-            const long rest = t256 - full * 256;
-            const int head_rows = (int)(full * 256 / tn) * 256;
-            if (full >= 1 && rest > 0 && rest < 160 && head_rows < p.M) {
-                GemmParams h = p, t = p;
-                h.M = head_rows;
-                if (int rc = launch<T, EPI, 8, 4, 2, 4>(h, s)) return rc;
-                const size_t es = sizeof(T);
-                t.M = p.M - head_rows;
-                t.A = static_cast<const char*>(p.A) + (size_t)head_rows * p.lda * es;
-                t.C = static_cast<char*>(p.C) + (size_t)head_rows * p.ldc * es;
-                if (p.R) t.R = static_cast<const char*>(p.R) + (size_t)head_rows * p.ldr * es;
-                if (p.H) t.H = static_cast<char*>(p.H) + (size_t)head_rows * p.ldh * es;
-                return launch_mt<T, EPI>(t, s, false);
-            }
+    }
+    // short K, wide N (qkv / fc1 / the fc2 activation gradient, K = 768): the last of the 3.5 - 4.6 rounds of 256 x 256 tiles is
+    // poorly filled.  Whole rounds of big tiles run on the leading rows, the remaining rows on the small tiles (qkv forward
+    // 151.7 -> 139.0 us; CLHIP_GEMM_TAIL=0 disables).  Only when the last round is < 160 of 256 tiles: a fuller one costs more as small tiles.
+    static const bool tail_split = !(clhip_cfg("GEMM_TAIL") != nullptr && atoi(clhip_cfg("GEMM_TAIL")) == 0);
+    if (allow_split && tail_split && !no_split && N % 256 == 0 && pick_tile(M, N) == 8) {
+        const int tn = N / 256;
+        const long t256 = (long)((M + 255) / 256) * tn;
+        const long full = t256 / 256;
+        const long rest = t256 - full * 256;
+        const int head_rows = (int)(full * 256 / tn) * 256;
+        if (full >= 1 && rest > 0 && rest < 160 && head_rows < M) {
+            r.add(CLHIP_GEMM_256, row0, head_rows, 1);
+            route_mt(r, row0 + head_rows, M - head_rows, N, K, f32, false, false);
+            return;
         }
-        switch (pick_tile(p.M, p.N)) {
-            case 8: return launch<T, EPI, 8, 4, 2, 4>(p, s);
-            case 5: return launch<T, EPI, 5, 4>(p, s);
-            case 2: return launch<T, EPI, 2, 2>(p, s);
-            default: return launch<T, EPI, 4, 4>(p, s);
-        }
+    }
+    switch (pick_tile(M, N)) {
+        case 8: r.add(CLHIP_GEMM_256, row0, M, 1); break;
+        case 5: r.add(CLHIP_GEMM_160, row0, M, 1); break;
+        case 2: r.add(CLHIP_GEMM_64, row0, M, 1); break;
+        default: r.add(CLHIP_GEMM_128, row0, M, 1); break;
     }
 }
 
-template <typename T> int dispatch(int epi, const GemmParams& p, hipStream_t s) {
+// the whole call: gemm8.hip takes the leading rows it asks for (whole rounds of its 256 persistent workgroups), the register-staged kernels the rest
+Route route_gemm(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype) {
+    Route r;
+    const int m8 = clhip_gemm8_rows(M, N, K, lda, ldb, ldc, ldr, ldh, dtype);
+    if (m8 > 0) r.add(CLHIP_GEMM_GEMM8, 0, m8 < M ? m8 : M, 1);
+    if (m8 < M) route_mt(r, m8 > 0 ? m8 : 0, m8 > 0 ? M - m8 : M, N, K, dtype != CLHIP_BF16, true, true);
+    return r;
+}
+
+// p restricted to rows [row0, row0 + rows)
+template <typename T> GemmParams rows_of(const GemmParams& p, int row0, int rows) {
+    GemmParams q = p;
+    const size_t es = sizeof(T);
+    q.M = rows;
+    q.A = static_cast<const char*>(p.A) + (size_t)row0 * p.lda * es;
+    q.C = static_cast<char*>(p.C) + (size_t)row0 * p.ldc * es;
+    if (p.R) q.R = static_cast<const char*>(p.R) + (size_t)row0 * p.ldr * es;
+    if (p.H) q.H = static_cast<char*>(p.H) + (size_t)row0 * p.ldh * es;
+    return q;
+}
+
+template <typename T, int EPI> int run_route(const GemmParams& p, const Route& r, hipStream_t s) {
+    if (r.overflow) { clhip_set_error("clhip_gemm_nt: the route has more than %d launches", Route::MAX); return CLHIP_EINVAL; }
+    for (int i = 0; i < r.n; ++i) {
+        const Launch& l = r.l[i];
+        GemmParams q = rows_of<T>(p, l.row0, l.rows);
+        int rc = CLHIP_OK;
+        if (l.kind == CLHIP_GEMM_GEMM8) {
+            rc = clhip_gemm8_launch(q.A, q.B, q.C, q.bias, q.R, q.H, q.M, q.N, q.K, q.lda, q.ldb, q.ldc, q.ldr, q.ldh, EPI, s);
+        } else if constexpr (sizeof(T) == 4) {
+            rc = launch<T, EPI, 4, 4>(q, s);
+        } else if (l.ks > 1) {
+            float* ws = splitk_scratch(s, (size_t)l.ks * q.M * q.N * sizeof(float));
+            if (ws == nullptr) {                              // no scratch right now (stream capture, allocation failure): the unsplit route of these rows
+                Route f;
+                route_mt(f, 0, q.M, q.N, q.K, false, true, false);
+                rc = run_route<T, EPI>(q, f, s);
+            } else {
+                q.ksplit = l.ks; q.part = ws + 1024; q.group_m = 1;
+                rc = launch<T, EPI, 4, 4>(q, s);
+            }
+        } else {
+            switch (l.kind) {
+                case CLHIP_GEMM_128: rc = launch<T, EPI, 4, 4>(q, s); break;
+                case CLHIP_GEMM_256: rc = launch<T, EPI, 8, 4, 2, 4>(q, s); break;
+                case CLHIP_GEMM_160: rc = launch<T, EPI, 5, 4>(q, s); break;
+                default: rc = launch<T, EPI, 2, 2>(q, s); break;
+            }
+        }
+        if (rc != CLHIP_OK) return rc;
+    }
+    return CLHIP_OK;
+}
+
+template <typename T> int dispatch(int epi, const GemmParams& p, const Route& r, hipStream_t s) {
     switch (epi) {
-        case EPI_NONE: return launch_mt<T, EPI_NONE>(p, s);
-        case EPI_BIAS: return launch_mt<T, EPI_BIAS>(p, s);
-        case EPI_BIAS_RES: return launch_mt<T, EPI_BIAS_RES>(p, s);
-        case EPI_BIAS_GELU: return launch_mt<T, EPI_BIAS_GELU>(p, s);
-        case EPI_MUL: return launch_mt<T, EPI_MUL>(p, s);
+        case EPI_NONE: return run_route<T, EPI_NONE>(p, r, s);
+        case EPI_BIAS: return run_route<T, EPI_BIAS>(p, r, s);
+        case EPI_BIAS_RES: return run_route<T, EPI_BIAS_RES>(p, r, s);
+        case EPI_BIAS_GELU: return run_route<T, EPI_BIAS_GELU>(p, r, s);
+        case EPI_MUL: return run_route<T, EPI_MUL>(p, r, s);
     }
     clhip_set_error("clhip_gemm_nt: unknown epilogue %d", epi);
     return CLHIP_EINVAL;
 }
 
-}  // namespace
-
-
-int clhip_gemm8_rows(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype);
-int clhip_gemm8_launch(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
-                       int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, hipStream_t st);
-
-extern "C" int clhip_gemm_nt(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
-                             int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, int dtype, void* stream) {
-    CLHIP_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0);
+// the shape and pitch rules of clhip_gemm_nt (include/clhip.h), shared with clhip_gemm_nt_route; with_r / with_h: R / H is given
+int check_shape(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype, bool with_r, bool with_h) {
+    CLHIP_CHECK_ARG(M > 0 && N > 0 && K > 0);
     CLHIP_CHECK_ARG(K % 64 == 0 && N % 4 == 0);
     CLHIP_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0);
     CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+    if (with_r) CLHIP_CHECK_ARG(ldr % 4 == 0);
+    if (with_h) CLHIP_CHECK_ARG(ldh % 4 == 0);
+    if (dtype == CLHIP_BF16 && N % 8 == 0 && (ldc % 8 != 0 || (with_r && ldr % 8 != 0) || (with_h && ldh % 8 != 0))) {
+        // the register-staged bf16 kernels move C, R and H of such a product as 16-byte chunks at row * ld + 8 c: every row must start 16-byte aligned
+        clhip_set_error("clhip_gemm_nt: bf16 with N %% 8 == 0 needs ldc, ldr, ldh %% 8 == 0 (16-byte row chunks); got ldc %d ldr %d ldh %d", ldc, ldr, ldh);
+        return CLHIP_EINVAL;
+    }
+    return CLHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int clhip_gemm_nt_route(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype, int* launches, int max_launches) {
+    if (int rc = check_shape(M, N, K, lda, ldb, ldc, ldr, ldh, dtype, true, true)) return rc;      // as a call that gives R and H
+    CLHIP_CHECK_ARG(max_launches >= 0 && (launches != nullptr || max_launches == 0));
+    const Route r = route_gemm(M, N, K, lda, ldb, ldc, ldr, ldh, dtype);
+    if (r.overflow) { clhip_set_error("clhip_gemm_nt_route: the route has more than %d launches", Route::MAX); return CLHIP_EINVAL; }
+    for (int i = 0; i < r.n && i < max_launches; ++i) {
+        launches[4 * i] = r.l[i].kind; launches[4 * i + 1] = r.l[i].row0; launches[4 * i + 2] = r.l[i].rows; launches[4 * i + 3] = r.l[i].ks;
+    }
+    return r.n;
+}
+
+extern "C" int clhip_gemm_nt(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
+                             int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, int dtype, void* stream) {
+    CLHIP_CHECK_ARG(A && B && C);
     if (epilogue == EPI_BIAS || epilogue == EPI_BIAS_RES || epilogue == EPI_BIAS_GELU) CLHIP_CHECK_ARG(bias != nullptr);
-    if (epilogue == EPI_BIAS_RES) CLHIP_CHECK_ARG(R != nullptr && ldr % 4 == 0);
+    if (epilogue == EPI_BIAS_RES) CLHIP_CHECK_ARG(R != nullptr);
     if (epilogue == EPI_MUL) CLHIP_CHECK_ARG(H != nullptr);
-    if (H) CLHIP_CHECK_ARG(ldh % 4 == 0);
+    if (int rc = check_shape(M, N, K, lda, ldb, ldc, ldr, ldh, dtype, R != nullptr, H != nullptr)) return rc;
     static const int gm_env = clhip_cfg("GEMM_GROUP_M") ? atoi(clhip_cfg("GEMM_GROUP_M")) : 0;
     GemmParams p{A, B, C, bias, R, H, M, N, K, lda, ldb, ldc, ldr, ldh, gm_env > 0 ? gm_env : (N >= 4096 ? 4 : 1)};     // wide outputs: 8192^3 991 -> 1046 TFLOP/s; the ViT shapes (N <= 3072) are indifferent
+    const Route r = route_gemm(M, N, K, lda, ldb, ldc, ldr, ldh, dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int m8 = clhip_gemm8_rows(M, N, K, lda, ldb, ldc, ldr, ldh, dtype)) {
-        // gemm8.hip takes the leading m8 rows (whole rounds of its 256 persistent workgroups), the register-staged kernel the rest
-        if (int rc = clhip_gemm8_launch(A, B, C, bias, R, H, m8, N, K, lda, ldb, ldc, ldr, ldh, epilogue, s)) return rc;
-        if (m8 >= M) return CLHIP_OK;
-        const size_t e = 2;                                    // bf16
-        A = static_cast<const char*>(A) + (size_t)m8 * lda * e;
-        C = static_cast<char*>(C) + (size_t)m8 * ldc * e;
-        if (R) R = static_cast<const char*>(R) + (size_t)m8 * ldr * e;
-        if (H) H = static_cast<char*>(H) + (size_t)m8 * ldh * e;
-        M -= m8;
-        p.A = A; p.C = C; p.R = R; p.H = H; p.M = M;
-        return dispatch<bf16_t>(epilogue, p, s);
-    }
-    return dtype == CLHIP_BF16 ? dispatch<bf16_t>(epilogue, p, s) : dispatch<float>(epilogue, p, s);
+    return dtype == CLHIP_BF16 ? dispatch<bf16_t>(epilogue, p, r, s) : dispatch<float>(epilogue, p, r, s);
 }

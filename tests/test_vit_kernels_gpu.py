@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_ref
 import vit_refs
 
 pytestmark = pytest.mark.gpu
@@ -53,17 +54,7 @@ def test_gemm_nt(dt, M, N, K, epi):
     Hin = rnd(M, N, seed=5).to(td)
     Cc = torch.empty(M, N, device=DEV, dtype=td)
     Hout = torch.zeros(M, N, device=DEV, dtype=td)
-    ref = A.double() @ B.double().T
-    if epi in (1, 2, 3):
-        ref = ref + bias.double()
-    if epi == 2:
-        ref = ref + R.double()
-    pre = ref.clone()
-    if epi == 3:        # C = gelu(pre), H = gelu'(pre)
-        ref = F.gelu(ref)
-        pre = 0.5 * (1 + torch.erf(pre / math.sqrt(2))) + pre * torch.exp(-0.5 * pre * pre) / math.sqrt(2 * math.pi)
-    if epi == 4:        # C = acc * H
-        ref = ref * Hin.double()
+    _, ref, pre = gemm_ref.gemm_ref(A, B, bias, R, Hin, epi)          # fp64: C, and for epilogue 3 H = gelu'
     Hp = Hout if epi == 3 else (Hin if epi == 4 else None)
     call("clhip_gemm_nt", p(A), p(B), p(Cc), p(bias) if epi in (1, 2, 3) else None, p(R) if epi == 2 else None, p(Hp), M, N, K, K, K, N, N, N, epi, CODE[dt], st())
     torch.cuda.synchronize()
@@ -87,17 +78,7 @@ def test_gemm8_every_epilogue(M, N, K, epi):
         Hin = rnd(M, N, seed=5).to(torch.bfloat16)
         Cc = torch.full((M + 1, N), 7.0, device=DEV, dtype=torch.bfloat16)          # one guard row behind the output
         Hout = torch.full((M + 1, N), 7.0, device=DEV, dtype=torch.bfloat16)
-        ref = A.double() @ B.double().T
-        if epi in (1, 2, 3):
-            ref = ref + bias.double()
-        if epi == 2:
-            ref = ref + R.double()
-        pre = ref.clone()
-        if epi == 3:
-            ref = F.gelu(ref)
-            pre = 0.5 * (1 + torch.erf(pre / math.sqrt(2))) + pre * torch.exp(-0.5 * pre * pre) / math.sqrt(2 * math.pi)
-        if epi == 4:
-            ref = ref * Hin.double()
+        _, ref, pre = gemm_ref.gemm_ref(A, B, bias, R, Hin, epi)          # fp64: C, and for epilogue 3 H = gelu'
         Hp = Hout if epi == 3 else (Hin if epi == 4 else None)
         call("clhip_gemm_nt", p(A), p(B), p(Cc), p(bias) if epi in (1, 2, 3) else None, p(R) if epi == 2 else None, p(Hp), M, N, K, K, K, N, N, N, epi, CODE["bf16"], st())
         torch.cuda.synchronize()
@@ -114,7 +95,8 @@ def test_gemm8_every_epilogue(M, N, K, epi):
 @pytest.mark.parametrize("epi", [0, 2, 3, 4])
 def test_gemm8_whole_rounds_and_a_register_staged_tail(M, N, K, epi):
     """mode 1 (what CLHIP_GEMM8=1 runs): gemm8.hip computes the row panels that fill whole rounds of its 256 workgroups, the register-staged
-    kernel the remaining rows (261 tiles -> 85 panels + 356 rows; 360 tiles -> 28 panels + 12 panels; 256 tiles -> all; 2 tiles -> none): one
+    kernel the remaining rows (as written: 261 tiles -> 85 panels + 356 rows; 360 tiles -> 28 panels + 12 panels; 256 tiles -> all; 2 tiles -> none.  Since gemm8 asks for 24
+    whole rounds x K tiles, clhip_gemm_nt_route reports the register-staged kernel alone for all four; tests/test_gemm_kernels_gpu.py has gemm8 + a tail): one
     result, every row written once, the guard row behind the output untouched"""
     _lib.lib().clhip_gemm8_config(1)
     try:
@@ -125,17 +107,7 @@ def test_gemm8_whole_rounds_and_a_register_staged_tail(M, N, K, epi):
         Hin = rnd(M, N, seed=15).to(torch.bfloat16)
         Cc = torch.full((M + 1, N), 7.0, device=DEV, dtype=torch.bfloat16)
         Hout = torch.full((M + 1, N), 7.0, device=DEV, dtype=torch.bfloat16)
-        ref = A.double() @ B.double().T
-        if epi in (1, 2, 3):
-            ref = ref + bias.double()
-        if epi == 2:
-            ref = ref + R.double()
-        pre = ref.clone()
-        if epi == 3:
-            ref = F.gelu(ref)
-            pre = 0.5 * (1 + torch.erf(pre / math.sqrt(2))) + pre * torch.exp(-0.5 * pre * pre) / math.sqrt(2 * math.pi)
-        if epi == 4:
-            ref = ref * Hin.double()
+        _, ref, pre = gemm_ref.gemm_ref(A, B, bias, R, Hin, epi)          # fp64: C, and for epilogue 3 H = gelu'
         Hp = Hout if epi == 3 else (Hin if epi == 4 else None)
         call("clhip_gemm_nt", p(A), p(B), p(Cc), p(bias) if epi in (1, 2, 3) else None, p(R) if epi == 2 else None, p(Hp), M, N, K, K, K, N, N, N, epi, CODE["bf16"], st())
         torch.cuda.synchronize()
@@ -161,17 +133,7 @@ def test_gemm_nt_split_k(M, N, K, epi):
     bias = rnd(N, seed=3)
     R = rnd(M, N, seed=4).to(torch.bfloat16)
     Hin = rnd(M, N, seed=5).to(torch.bfloat16)
-    ref = A.double() @ B.double().T
-    if epi in (1, 2, 3):
-        ref = ref + bias.double()
-    if epi == 2:
-        ref = ref + R.double()
-    pre = ref.clone()
-    if epi == 3:
-        ref = F.gelu(ref)
-        pre = 0.5 * (1 + torch.erf(pre / math.sqrt(2))) + pre * torch.exp(-0.5 * pre * pre) / math.sqrt(2 * math.pi)
-    if epi == 4:
-        ref = ref * Hin.double()
+    _, ref, pre = gemm_ref.gemm_ref(A, B, bias, R, Hin, epi)          # fp64: C, and for epilogue 3 H = gelu'
     outs = []
     for _ in range(2):
         Cc = torch.full((M + 1, N), 7.0, device=DEV, dtype=torch.bfloat16)
