@@ -482,6 +482,35 @@ int clhip_conv_bn_input_wt_supported(int N, int H, int W, int C, int K, int ksiz
 int clhip_conv_fwd_acc_bn_input_wt(const void* z_in, const clhip_bn_input* bn /*host*/, const clhip_bn_res_input* rs /*host*/, const void* w_fwd, void* z,
                                    double* stat_acc, int replicas, int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype,
                                    void* stream);
+/* Which kernel a convolution call would run (host code only: no device, no pointers).  op: 0 clhip_conv_fwd / _acc, 1 clhip_conv_dgrad, 2 clhip_conv_wgrad,
+ * 3 clhip_conv_dgrad_bn_reduce[_ex], 4 clhip_conv_fwd_acc_bn_input_wt.  form: forward 0 no statistics, 1 partial rows (stat_partials), 2 fp64 accumulators
+ * (_acc); wgrad 0 ws == NULL, 1 scratch given; otherwise 0.  Returns one kernel family below (> 0), or CLHIP_EINVAL with clhip_last_error set where the call
+ * would refuse these shapes (the same check; pointer arguments are the call's own business).  The five entry points switch on this function's result; the
+ * current clhip_config switches apply (most are cached at their first use). */
+#define CLHIP_CONV_STEM7 1         /* stem7.hip forward (7x7 / s2 / p3) */
+#define CLHIP_CONV_STEM 2          /* stem.hip forward (3x3, 8 padded input channels) */
+#define CLHIP_CONV_CONV64 3        /* conv3.hip conv64_kernel */
+#define CLHIP_CONV_CONV16 4        /* conv3.hip conv16_kernel / conv32_kernel */
+#define CLHIP_CONV_CONV8 5         /* conv8.hip */
+#define CLHIP_CONV_CONV5 6         /* conv5.hip */
+#define CLHIP_CONV_CONV9 7         /* conv9.hip */
+#define CLHIP_CONV_CONV4 8         /* conv4.hip */
+#define CLHIP_CONV_CONV3 9         /* conv3.hip conv3_kernel / conv3g_kernel */
+#define CLHIP_CONV_CONV2 10        /* conv2.hip conv_igemm2_kernel (the generic kernel) */
+#define CLHIP_CONV_V1 11           /* conv.hip conv_igemm_kernel (CONV_V1) */
+#define CLHIP_CONV_SHORTCUT 12     /* shortcut.hip (dgrad of the 1x1 / s2 shortcut) */
+#define CLHIP_CONV_WGRAD_STEM7 13  /* stem7.hip weight gradient */
+#define CLHIP_CONV_WGRAD_STEM 14   /* stem.hip weight gradient */
+#define CLHIP_CONV_WGRAD64 15      /* conv3.hip wgrad64_kernel */
+#define CLHIP_CONV_WGRAD4 16       /* wgrad4.hip */
+#define CLHIP_CONV_WGRAD3 17       /* conv3.hip conv_wgrad3_kernel */
+#define CLHIP_CONV_WGRAD16 18      /* conv3.hip wgrad16_kernel */
+#define CLHIP_CONV_WGRAD32 19      /* conv3.hip wgrad32_kernel */
+#define CLHIP_CONV_WGRAD2_DET 20   /* conv2.hip conv_wgrad2_kernel, partial blocks + fixed-order reduce */
+#define CLHIP_CONV_WGRAD2_ATOMIC 21 /* conv2.hip conv_wgrad2_kernel, fp32 atomics */
+#define CLHIP_CONV_WGRAD_V1 22     /* conv.hip conv_wgrad_kernel (CONV_V1), LDS transpose read in bf16 */
+#define CLHIP_CONV_WGRAD_V1_NO_TR 23 /* conv.hip conv_wgrad_kernel without the transpose read (WGRAD_NO_TR; fp32 always) */
+int clhip_conv_route(int op, int form, int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
 int clhip_conv_dgrad_wgrad_bn_input(const void* x_z, const float* x_coef, const void* dz, const void* w_dg, void* dx, int accumulate, float* dw,
                                     void* ws, const float* mean, const float* invstd, double* acc /*nullable*/, int replicas, int N, int H, int W,
                                     int C, int Creal, int K, int ksize, int stride, int pad, int dtype, void* stream);

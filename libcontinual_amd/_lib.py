@@ -13,6 +13,9 @@ LIB_PATH = os.path.join(_HERE, "libclhip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "clhip.h")
 
 BF16, F32 = 0, 1
+# kernel families of clhip_conv_route (include/clhip.h, CLHIP_CONV_*)
+(CONV_STEM7, CONV_STEM, CONV_CONV64, CONV_CONV16, CONV_CONV8, CONV_CONV5, CONV_CONV9, CONV_CONV4, CONV_CONV3, CONV_CONV2, CONV_V1, CONV_SHORTCUT, CONV_WGRAD_STEM7,
+ CONV_WGRAD_STEM, CONV_WGRAD64, CONV_WGRAD4, CONV_WGRAD3, CONV_WGRAD16, CONV_WGRAD32, CONV_WGRAD2_DET, CONV_WGRAD2_ATOMIC, CONV_WGRAD_V1, CONV_WGRAD_V1_NO_TR) = range(1, 24)
 
 
 class ClhipError(RuntimeError):
@@ -161,6 +164,7 @@ _PROTOS = {
     "clhip_augment_rrc_aa": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),
     "clhip_gemm_nt": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 10 + [_p]),
     "clhip_gemm_nt_route": (_i, [_i] * 9 + [C.POINTER(C.c_int), _i]),
+    "clhip_conv_route": (_i, [_i] * 12),
     "clhip_config": (_i, [C.c_char_p, C.c_char_p]),
     "clhip_config_get": (C.c_char_p, [C.c_char_p]),
     "clhip_conv_bn_input_wt_supported": (_i, [_i] * 9),

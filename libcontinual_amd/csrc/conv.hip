@@ -531,6 +531,105 @@ extern "C" int clhip_conv_fwd_tiles(int N, int H, int W, int C, int K, int ksize
 
 static bool conv64_fwd_on() { const char* c = clhip_cfg("CONV64_FWD"); return !(c != nullptr && atoi(c) == 0); }
 
+static bool wgrad_v1_no_tr() { static const bool v = clhip_cfg("WGRAD_NO_TR") != nullptr; return v; }
+bool clhip_conv4_in_supported(int N, int H, int W, int Cs, int Cd);      // conv4.hip
+
+// ONE decision for clhip_conv_fwd[_acc], clhip_conv_dgrad, clhip_conv_wgrad, clhip_conv_dgrad_bn_reduce_ex, clhip_conv_fwd_acc_bn_input_wt and clhip_conv_route
+// (include/clhip.h: op, form and the CLHIP_CONV_* families): the shared argument check, then the kernels in their order of preference.  The entry
+// points switch on the result; pointer arguments stay their own business.  CLHIP_EINVAL (error text set) where the call refuses.
+enum { OP_FWD = 0, OP_DGRAD = 1, OP_WGRAD = 2, OP_DGRAD_BNR = 3, OP_FWD_WT = 4 };
+static int route_conv(int op, int form, int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
+    CLHIP_CHECK_ARG(op >= OP_FWD && op <= OP_FWD_WT);
+    CLHIP_CHECK_ARG(form >= 0 && form <= (op == OP_FWD ? 2 : (op == OP_WGRAD ? 1 : 0)));
+    if (ksize == 7 && (op == OP_FWD || op == OP_WGRAD)) {
+        // the ImageNet stem (<= 8 padded input channels, stride 2, pad 3): stem7.hip, both dtypes
+        CLHIP_CHECK_ARG(clhip_stem7_supported(N, H, W, C, K, stride, pad));
+        if (op == OP_FWD) CLHIP_CHECK_ARG(form != 1);                                                            // statistics through the accumulators only
+        else CLHIP_CHECK_ARG(form == 1 && Creal >= 1 && Creal <= C && (K * 49 * Creal) % 4 == 0);                // partial blocks + fixed-order reduce: there is no atomic form
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        return op == OP_FWD ? CLHIP_CONV_STEM7 : CLHIP_CONV_WGRAD_STEM7;
+    }
+    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
+    const bool v2 = !use_v1();               // the second-generation generic kernels (conv2.hip)
+    const bool v3 = v2 && use_v3();          // the specialised kernels
+    if (op == OP_FWD) {
+        CLHIP_CHECK_ARG(!(form == 2 && !v2));
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        const bool rows = form == 1;         // partial rows: only the kernels that write them
+        // the stems (<= 8 padded input channels): no LDS, weights in registers; serves the accumulator and the no-statistics forms
+        if (v3 && !rows && clhip_stem_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_STEM;
+        // 64 -> 64 channels on small maps: register-resident filters, out channels split over the waves (statistics through the accumulators only)
+        if (v3 && !rows && conv64_fwd_on() && clhip_conv64_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV64;
+        if (v3 && clhip_conv16_supported(H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV16;
+        // 64 -> 64 channels on large activations: two four-wave workgroups per CU, the filters of 32 output channels resident in each wave (conv8.hip) ...
+        if (v3 && !rows && clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV8;
+        // ... or the weight-stationary kernel with one 512-register wave per SIMD (statistics through the accumulators only)
+        if (v3 && !rows && clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV5;
+        // 128 -> 128 / 256 -> 256 channels: resident patch, one barrier per 32-KB filter slab (conv9.hip; statistics through the accumulators only)
+        if (v3 && !rows && clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV9;
+        if (v3 && clhip_conv4_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV4;
+        if (v3 && clhip_conv3_supported(H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV3;
+        return v2 ? CLHIP_CONV_CONV2 : CLHIP_CONV_V1;
+    }
+    if (op == OP_DGRAD) {
+        CLHIP_CHECK_ARG(C % 16 == 0);
+        CLHIP_CHECK_ARG(ilog2_exact(K) >= 0);
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        if (v3 && clhip_shortcut_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_SHORTCUT;
+        if (v3 && clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV16;
+        if (v3 && clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV64;
+        if (v3 && clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV8;
+        if (v3 && clhip_conv5_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV5;
+        if (v3 && clhip_conv9_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV9;
+        if (v3 && clhip_conv4_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV4;
+        if (v3 && clhip_conv3_supported(H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV3;
+        return v2 ? CLHIP_CONV_CONV2 : CLHIP_CONV_V1;
+    }
+    if (op == OP_WGRAD) {
+        CLHIP_CHECK_ARG(Creal >= 1 && Creal <= C);
+        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
+        const bool ws = form == 1;
+        if (v3 && ws && clhip_stem_wgrad_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD_STEM;
+        if (v3 && ws && clhip_wgrad64_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD64;
+        if (v3 && ws && clhip_wgrad4_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD4;
+        if (v3 && clhip_wgrad3_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD3;
+        if (v3 && ws && clhip_wgrad16_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD16;
+        if (v3 && ws && clhip_wgrad32_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype)) return CLHIP_CONV_WGRAD32;
+        // the generic kernel: with scratch (and a gradient the reduce can take) per-split partial blocks + the fixed-order reduce, else fp32 atomics
+        if (v2) return (ws && clhip_wgrad2_ws_bytes(N, H, W, C, Creal, K, ksize, stride, pad) > 0) ? CLHIP_CONV_WGRAD2_DET : CLHIP_CONV_WGRAD2_ATOMIC;
+        return (dtype == CLHIP_BF16 && !wgrad_v1_no_tr()) ? CLHIP_CONV_WGRAD_V1 : CLHIP_CONV_WGRAD_V1_NO_TR;
+    }
+    if (op == OP_DGRAD_BNR) {
+        // the kernels whose dgrad epilogue reduces the producer's BatchNorm-backward sums (bf16 only); conv9 where one of the others would serve
+        CLHIP_CHECK_ARG(v3 && (clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype) || clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype) ||
+                               clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype) || clhip_conv4_supported(N, H, W, K, C, ksize, stride, pad, dtype)));
+        if (clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV64;
+        if (clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV16;      // 16 -> 16 / 32 -> 32 channels: the register-resident kernels' epilogue
+        if (clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV8;
+        if (clhip_conv9_supported(N, H, W, K, C, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV9;
+        return CLHIP_CONV_CONV4;
+    }
+    // OP_FWD_WT
+    CLHIP_CHECK_ARG(v3 && dtype == CLHIP_BF16);
+    // OFF by default (BN_INPUT_WT=1 enables it): measured on ResNet-18 layer1 at batch 256 the fused launch is 41.5 us against 47.2 us for the two it
+    // replaces stand-alone, but inside the step the apply launches run at 10-11 us out of the Infinity Cache and the step got SLOWER (2.095 ->
+    // 2.14 ms with the four layer-1 units fused; the +res form loses stand-alone as well: 59 vs 55 us) -- profiles/r04_wt_notes.md
+    // (round 5: conv8.hip hides the transform under the other workgroup's MFMAs, and the step is still neutral -- 2.00-2.06 vs 2.00-2.03 ms: the layer is
+    //  HBM-bound, the fused launch re-reads the halo rows of z' AND r (1.55 x each at 128-pixel tiles) and saves one read of the activation)
+    const char* cfg = clhip_cfg("BN_INPUT_WT");
+    CLHIP_CHECK_ARG(cfg != nullptr && atoi(cfg) != 0);
+    CLHIP_CHECK_ARG(!(conv64_fwd_on() && clhip_conv64_supported(N, H, W, C, K, ksize, stride, pad, dtype)));      // (that layer runs on the register-staged kernel)
+    if (clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV8;
+    if (clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV9;
+    if (clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV5;
+    CLHIP_CHECK_ARG(clhip_conv4_supported(N, H, W, C, K, ksize, stride, pad, dtype) && clhip_conv4_in_supported(N, H, W, C, K));
+    return CLHIP_CONV_CONV4;
+}
+
+extern "C" int clhip_conv_route(int op, int form, int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
+    return route_conv(op, form, N, H, W, C, Creal, K, ksize, stride, pad, dtype);
+}
+
 static int conv_fwd_impl(const void* x, const void* w_fwd, void* z, float* stat_partials, double* stat_acc, int stat_rep, int N, int H, int W, int C,
                          int K, int ksize, int stride, int pad, int dtype, void* stream);
 
@@ -547,108 +646,79 @@ extern "C" int clhip_conv_fwd_acc(const void* x, const void* w_fwd, void* z, dou
 
 static int conv_fwd_impl(const void* x, const void* w_fwd, void* z, float* stat_partials, double* stat_acc, int stat_rep, int N, int H, int W, int C,
                          int K, int ksize, int stride, int pad, int dtype, void* stream) {
-    if (ksize == 7) {
-        // the ImageNet stem (<= 8 padded input channels, stride 2, pad 3): stem7.hip, both dtypes; statistics through the accumulators only
-        CLHIP_CHECK_ARG(clhip_stem7_supported(N, H, W, C, K, stride, pad) && x && w_fwd && z && stat_partials == nullptr);
-        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
-        return clhip_stem7_fwd_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, dtype, static_cast<hipStream_t>(stream));
-    }
-    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
+    const int family = route_conv(OP_FWD, stat_partials ? 1 : (stat_acc ? 2 : 0), N, H, W, C, C, K, ksize, stride, pad, dtype);
+    if (family < 0) return family;
     CLHIP_CHECK_ARG(x && w_fwd && z);
-    CLHIP_CHECK_ARG(!(stat_acc && use_v1()));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (family == CLHIP_CONV_STEM7) return clhip_stem7_fwd_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, dtype, st);
     ConvParams p;
     p.src = x; p.wt = w_fwd; p.dst = z; p.stats = stat_partials;
     p.N = N; p.Hs = H; p.Ws = W; p.Cs = C; p.log2Cs = ilog2_exact(C);
     p.Hd = (H + 2 * pad - ksize) / stride + 1; p.Wd = (W + 2 * pad - ksize) / stride + 1; p.Cd = K;
     p.ksize = ksize; p.stride = stride; p.pad = pad; p.accumulate = 0;
     p.M = N * p.Hd * p.Wd; p.K = ksize * ksize * C;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
-    // the stems (<= 8 padded input channels): no LDS, weights in registers; serves the accumulator and the no-statistics forms
-    if (!use_v1() && use_v3() && stat_partials == nullptr && clhip_stem_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_stem_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, st);
-    // 64 -> 64 channels on small maps: register-resident filters, out channels split over the waves (statistics through the accumulators only)
-    if (!use_v1() && use_v3() && stat_partials == nullptr && conv64_fwd_on() && clhip_conv64_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv64_launch_ex(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
-    if (!use_v1() && use_v3() && clhip_conv16_supported(H, W, C, K, ksize, stride, pad, dtype)) {
-        int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
-        int tiles_used = clhip_conv16_tiles_m(p.M);
+    // the caller's partial buffer may hold more tiles than the kernel writes: zero the tail rows
+    auto zero_tail = [&](int tiles_used) {
+        const int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
         if (stat_partials && tiles_alloc > tiles_used)
             hipMemsetAsync(stat_partials + (size_t)tiles_used * 2 * K, 0, (size_t)(tiles_alloc - tiles_used) * 2 * K * sizeof(float), st);
-        return clhip_conv16_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, 0, 0, st);
+    };
+    switch (family) {
+        case CLHIP_CONV_STEM: return clhip_stem_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, st);
+        case CLHIP_CONV_CONV64:
+            return clhip_conv64_launch_ex(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
+        case CLHIP_CONV_CONV16:
+            zero_tail(clhip_conv16_tiles_m(p.M));
+            return clhip_conv16_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, 0, 0, st);
+        case CLHIP_CONV_CONV8:
+            return clhip_conv8_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV4:
+            zero_tail(clhip_conv4_tiles_m(p.M, C, K, W));
+            return clhip_conv4_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
+        case CLHIP_CONV_CONV3:
+            zero_tail(clhip_conv3_tiles_m(p.M, K));
+            return clhip_conv3_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
+        case CLHIP_CONV_CONV2:
+            zero_tail(clhip_conv2_tiles_m(p.M, K));
+            return clhip_conv2_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, p.Hd, p.Wd, K, ksize, stride, pad, 0, 0, dtype, st);
+        case CLHIP_CONV_V1: return dtype == CLHIP_BF16 ? launch_igemm<bf16_t, 0>(p, st) : launch_igemm<float, 0>(p, st);
+        default: break;
     }
-    // 64 -> 64 channels on large activations: two four-wave workgroups per CU, the filters of 32 output channels resident in each wave (conv8.hip) ...
-    if (!use_v1() && use_v3() && stat_partials == nullptr && clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv8_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    // ... or the weight-stationary kernel with one 512-register wave per SIMD (statistics through the accumulators only)
-    if (!use_v1() && use_v3() && stat_partials == nullptr && clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv5_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, st);
-    // 128 -> 128 / 256 -> 256 channels: resident patch, one barrier per 32-KB filter slab (conv9.hip; statistics through the accumulators only)
-    if (!use_v1() && use_v3() && stat_partials == nullptr && clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv9_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv4_supported(N, H, W, C, K, ksize, stride, pad, dtype)) {
-        int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
-        int tiles_used = clhip_conv4_tiles_m(p.M, C, K, W);
-        if (stat_partials && tiles_alloc > tiles_used)
-            hipMemsetAsync(stat_partials + (size_t)tiles_used * 2 * K, 0, (size_t)(tiles_alloc - tiles_used) * 2 * K * sizeof(float), st);
-        return clhip_conv4_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
-    }
-    if (!use_v1() && use_v3() && clhip_conv3_supported(H, W, C, K, ksize, stride, pad, dtype)) {
-        // the caller's partial buffer may hold more tiles than this kernel writes: zero the tail rows
-        int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
-        int tiles_used = clhip_conv3_tiles_m(p.M, K);
-        if (stat_partials && tiles_alloc > tiles_used)
-            hipMemsetAsync(stat_partials + (size_t)tiles_used * 2 * K, 0, (size_t)(tiles_alloc - tiles_used) * 2 * K * sizeof(float), st);
-        return clhip_conv3_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
-    }
-    if (!use_v1()) {
-        int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
-        int tiles_used = clhip_conv2_tiles_m(p.M, K);
-        if (stat_partials && tiles_alloc > tiles_used)
-            hipMemsetAsync(stat_partials + (size_t)tiles_used * 2 * K, 0, (size_t)(tiles_alloc - tiles_used) * 2 * K * sizeof(float), st);
-        return clhip_conv2_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, p.Hd, p.Wd, K, ksize, stride, pad, 0, 0, dtype, st);
-    }
-    if (dtype == CLHIP_BF16) return launch_igemm<bf16_t, 0>(p, st);
-    if (dtype == CLHIP_F32) return launch_igemm<float, 0>(p, st);
-    CLHIP_CHECK_ARG(!"dtype");
+    clhip_set_error("clhip_conv_fwd: no launch for kernel family %d", family);
     return CLHIP_EINVAL;
 }
 
 extern "C" int clhip_conv_dgrad(const void* dz, const void* w_dg, void* dx, int accumulate, int N, int H, int W, int C,
                                 int K, int ksize, int stride, int pad, int dtype, void* stream) {
-    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
+    const int family = route_conv(OP_DGRAD, 0, N, H, W, C, C, K, ksize, stride, pad, dtype);
+    if (family < 0) return family;
     CLHIP_CHECK_ARG(dz && w_dg && dx);
-    CLHIP_CHECK_ARG(C % 16 == 0);
     ConvParams p;
     p.src = dz; p.wt = w_dg; p.dst = dx; p.stats = nullptr;
     p.N = N; p.Hs = (H + 2 * pad - ksize) / stride + 1; p.Ws = (W + 2 * pad - ksize) / stride + 1; p.Cs = K;
     p.log2Cs = ilog2_exact(K);
-    CLHIP_CHECK_ARG(p.log2Cs >= 0);
     p.Hd = H; p.Wd = W; p.Cd = C;
     p.ksize = ksize; p.stride = stride; p.pad = pad; p.accumulate = accumulate;
     p.M = N * H * W; p.K = ksize * ksize * K;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
-    if (!use_v1() && use_v3() && clhip_shortcut_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_shortcut_dgrad(dz, w_dg, dx, accumulate, N, H, W, C, K, st);
-    if (!use_v1() && use_v3() && clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv16_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
-    if (!use_v1() && use_v3() && clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv5_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv5_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv9_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv4_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv4_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
-    if (!use_v1() && use_v3() && clhip_conv3_supported(H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv3_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
-    if (!use_v1()) return clhip_conv2_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, p.Hs, p.Ws, K, H, W, C, ksize, stride, pad, accumulate, 1, dtype, st);
-    if (dtype == CLHIP_BF16) return launch_igemm<bf16_t, 1>(p, st);
-    if (dtype == CLHIP_F32) return launch_igemm<float, 1>(p, st);
-    CLHIP_CHECK_ARG(!"dtype");
+    switch (family) {
+        case CLHIP_CONV_SHORTCUT: return clhip_shortcut_dgrad(dz, w_dg, dx, accumulate, N, H, W, C, K, st);
+        case CLHIP_CONV_CONV16: return clhip_conv16_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, st);
+        case CLHIP_CONV_CONV64:
+            return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
+        case CLHIP_CONV_CONV8:
+            return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV4: return clhip_conv4_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
+        case CLHIP_CONV_CONV3: return clhip_conv3_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
+        case CLHIP_CONV_CONV2: return clhip_conv2_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, p.Hs, p.Ws, K, H, W, C, ksize, stride, pad, accumulate, 1, dtype, st);
+        case CLHIP_CONV_V1: return dtype == CLHIP_BF16 ? launch_igemm<bf16_t, 1>(p, st) : launch_igemm<float, 1>(p, st);
+        default: break;
+    }
+    clhip_set_error("clhip_conv_dgrad: no launch for kernel family %d", family);
     return CLHIP_EINVAL;
 }
 
@@ -656,10 +726,7 @@ int clhip_conv16_launch_bn(const void* src, const void* wt, void* dst, float* st
                            const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st);      // conv3.hip
 
 extern "C" int clhip_conv_dgrad_bn_reduce_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype) {
-    if (check_conv(N, H, W, C, K, ksize, stride, pad) != CLHIP_OK) return 0;
-    if (use_v1() || !use_v3()) return 0;
-    return (clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype) || clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype) ||
-            clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype) || clhip_conv4_supported(N, H, W, K, C, ksize, stride, pad, dtype)) ? 1 : 0;
+    return route_conv(OP_DGRAD_BNR, 0, N, H, W, C, C, K, ksize, stride, pad, dtype) > 0 ? 1 : 0;
 }
 
 // ... and where that epilogue is hidden (conv8.hip: the other workgroup of the CU multiplies meanwhile), so that the plan fuses it on large maps too
@@ -684,23 +751,23 @@ extern "C" int clhip_conv_dgrad_bn_reduce(const void* dz, const void* w_dg, void
 extern "C" int clhip_conv_dgrad_bn_reduce_ex(const void* dz, const void* w_dg, void* dx, int accumulate, const void* z_prod, const void* y_prod, const void* mask_prod,
                                              const float* gamma_prod, const float* beta_prod, const float* mean, const float* invstd, double* acc, int replicas, int N, int H, int W, int C,
                                              int K, int ksize, int stride, int pad, int dtype, void* stream) {
-    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
+    const int family = route_conv(OP_DGRAD_BNR, 0, N, H, W, C, C, K, ksize, stride, pad, dtype);
+    if (family < 0) return family;
     CLHIP_CHECK_ARG(dz && w_dg && dx && z_prod && mean && invstd && acc);
     CLHIP_CHECK_ARG(replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0);
-    CLHIP_CHECK_ARG(clhip_conv_dgrad_bn_reduce_supported(N, H, W, C, K, ksize, stride, pad, dtype));
-    if (clhip_conv64_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, nullptr, nullptr,
-                                      static_cast<hipStream_t>(stream));
-    if (clhip_conv16_supported(H, W, K, C, ksize, stride, pad, dtype))      // 16 -> 16 / 32 -> 32 channels: the register-resident kernels' epilogue
-        return clhip_conv16_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas,
-                                      static_cast<hipStream_t>(stream));
-    if (clhip_conv8_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, z_prod, y_prod, mask_prod, gamma_prod, beta_prod, mean, invstd, acc, replicas,
-                                  static_cast<hipStream_t>(stream));
-    if (clhip_conv9_supported(N, H, W, K, C, ksize, stride, pad, dtype))
-        return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, z_prod, y_prod, mean, invstd, acc, replicas, static_cast<hipStream_t>(stream));
-    return clhip_conv4_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas,
-                                 static_cast<hipStream_t>(stream));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (family) {
+        case CLHIP_CONV_CONV64:
+            return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, nullptr, nullptr, st);
+        case CLHIP_CONV_CONV16: return clhip_conv16_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, st);
+        case CLHIP_CONV_CONV8:
+            return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, z_prod, y_prod, mask_prod, gamma_prod, beta_prod, mean, invstd, acc, replicas, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, z_prod, y_prod, mean, invstd, acc, replicas, st);
+        case CLHIP_CONV_CONV4: return clhip_conv4_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, st);
+        default: break;
+    }
+    clhip_set_error("clhip_conv_dgrad_bn_reduce: no launch for kernel family %d", family);
+    return CLHIP_EINVAL;
 }
 
 bool clhip_bwd_fused_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);      // conv3.hip
@@ -764,31 +831,17 @@ bool clhip_conv4_in_supported(int N, int H, int W, int Cs, int Cd);
 int clhip_conv4_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, const LazyIn* in, hipStream_t st);
 
 extern "C" int clhip_conv_bn_input_wt_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype) {
-    if (check_conv(N, H, W, C, K, ksize, stride, pad) != CLHIP_OK) return 0;
-    if (use_v1() || !use_v3() || dtype != CLHIP_BF16) return 0;
-    // OFF by default (BN_INPUT_WT=1 enables it): measured on ResNet-18 layer1 at batch 256 the fused launch is 41.5 us against 47.2 us for the two it
-    // replaces stand-alone, but inside the step the apply launches run at 10-11 us out of the Infinity Cache and the step got SLOWER (2.095 ->
-    // 2.14 ms with the four layer-1 units fused; the +res form loses stand-alone as well: 59 vs 55 us) -- profiles/r04_wt_notes.md
-    // (round 5: conv8.hip hides the transform under the other workgroup's MFMAs, and the step is still neutral -- 2.00-2.06 vs 2.00-2.03 ms: the layer is
-    //  HBM-bound, the fused launch re-reads the halo rows of z' AND r (1.55 x each at 128-pixel tiles) and saves one read of the activation)
-    const char* cfg = clhip_cfg("BN_INPUT_WT");
-    if (cfg == nullptr || atoi(cfg) == 0) return 0;
-    if (conv64_fwd_on() && clhip_conv64_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return 0;      // (that layer runs on the register-staged kernel)
-    if (clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return 1;
-    if (clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return 1;
-    if (clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return 1;
-    if (clhip_conv4_supported(N, H, W, C, K, ksize, stride, pad, dtype) && clhip_conv4_in_supported(N, H, W, C, K)) return 1;
-    return 0;
+    return route_conv(OP_FWD_WT, 0, N, H, W, C, C, K, ksize, stride, pad, dtype) > 0 ? 1 : 0;      // (why it is off by default: route_conv)
 }
 
 extern "C" int clhip_conv_fwd_acc_bn_input_wt(const void* z_in, const clhip_bn_input* bn, const clhip_bn_res_input* rs, const void* w_fwd, void* z, double* stat_acc,
                                               int replicas, int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype, void* stream) {
-    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
+    const int family = route_conv(OP_FWD_WT, 0, N, H, W, C, C, K, ksize, stride, pad, dtype);
+    if (family < 0) return family;
     CLHIP_CHECK_ARG(z_in && bn && rs && rs->y && w_fwd && z && stat_acc && replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0);
     CLHIP_CHECK_ARG(bn->stat_acc && bn->gamma && bn->beta && bn->mean && bn->invstd && bn->coef && bn->replicas >= 1 && bn->replicas <= 64);
     CLHIP_CHECK_ARG((bn->running_mean == nullptr) == (bn->running_var == nullptr));
     CLHIP_CHECK_ARG(rs->relu_mask == nullptr || rs->res != nullptr);
-    CLHIP_CHECK_ARG(clhip_conv_bn_input_wt_supported(N, H, W, C, K, ksize, stride, pad, dtype));
     LazyIn in;
     in.acc = bn->stat_acc; in.rep = bn->replicas; in.gamma = bn->gamma; in.beta = bn->beta; in.rm = bn->running_mean; in.rv = bn->running_var;
     in.momentum = bn->momentum; in.eps = bn->eps; in.mean_o = bn->mean; in.invstd_o = bn->invstd; in.coef_o = bn->coef;
@@ -796,12 +849,16 @@ extern "C" int clhip_conv_fwd_acc_bn_input_wt(const void* z_in, const clhip_bn_i
     in.invM = 1.0 / M; in.unbias = M > 1.0 ? M / (M - 1.0) : 1.0;
     in.res = static_cast<const bf16_t*>(rs->res); in.y = static_cast<bf16_t*>(rs->y); in.mask = static_cast<unsigned char*>(rs->relu_mask);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv8_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    if (clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype))
-        return clhip_conv9_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-    if (clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return clhip_conv5_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, st);
-    return clhip_conv4_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, K, &in, st);
+    switch (family) {
+        case CLHIP_CONV_CONV8:
+            return clhip_conv8_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, st);
+        case CLHIP_CONV_CONV4: return clhip_conv4_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, K, &in, st);
+        default: break;
+    }
+    clhip_set_error("clhip_conv_fwd_acc_bn_input_wt: no launch for kernel family %d", family);
+    return CLHIP_EINVAL;
 }
 
 extern "C" int clhip_conv_dgrad_wgrad_bn_input(const void* x_z, const float* x_coef, const void* dz, const void* w_dg, void* dx, int accumulate, float* dw,
@@ -961,14 +1018,27 @@ static size_t wgrad_ws_bytes_single(int N, int H, int W, int C, int Creal, int K
 
 extern "C" int clhip_conv_wgrad(const void* x, const void* dz, float* dw, void* ws, int N, int H, int W, int C, int Creal, int K,
                                 int ksize, int stride, int pad, int dtype, void* stream) {
-    if (ksize == 7) {
-        // stem7.hip: partial blocks + fixed-order reduce (the scratch is required: there is no atomic form)
-        CLHIP_CHECK_ARG(clhip_stem7_supported(N, H, W, C, K, stride, pad) && x && dz && dw && ws && Creal >= 1 && Creal <= C && (K * 49 * Creal) % 4 == 0);
-        CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
-        return clhip_stem7_wgrad_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, Creal, K, dtype, static_cast<hipStream_t>(stream));
+    const int family = route_conv(OP_WGRAD, ws != nullptr ? 1 : 0, N, H, W, C, Creal, K, ksize, stride, pad, dtype);
+    if (family < 0) return family;
+    CLHIP_CHECK_ARG(x && dz && dw);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* wsf = static_cast<float*>(ws);
+    switch (family) {
+        case CLHIP_CONV_WGRAD_STEM7: return clhip_stem7_wgrad_launch(x, dz, dw, wsf, N, H, W, Creal, K, dtype, st);
+        case CLHIP_CONV_WGRAD_STEM: return clhip_stem_wgrad_launch(x, dz, dw, wsf, N, H, W, Creal, K, st);
+        case CLHIP_CONV_WGRAD64: return clhip_wgrad64_launch(x, dz, dw, wsf, N, H, nullptr, st);
+        case CLHIP_CONV_WGRAD4: return clhip_wgrad4_launch(x, dz, dw, wsf, N, H, W, C, K, ksize, stride, st);
+        case CLHIP_CONV_WGRAD3: return clhip_wgrad3_launch(x, dz, dw, wsf, N, H, W, C, Creal, K, st);
+        case CLHIP_CONV_WGRAD16: return clhip_wgrad16_launch(x, dz, dw, wsf, N, H, nullptr, st);
+        case CLHIP_CONV_WGRAD32: return clhip_wgrad32_launch(x, dz, dw, wsf, N, H, nullptr, st);
+        case CLHIP_CONV_WGRAD2_DET: return clhip_wgrad2_launch(x, dz, dw, wsf, N, H, W, C, Creal, K, ksize, stride, pad, dtype, st);
+        case CLHIP_CONV_WGRAD2_ATOMIC: return clhip_wgrad2_launch(x, dz, dw, nullptr, N, H, W, C, Creal, K, ksize, stride, pad, dtype, st);
+        case CLHIP_CONV_WGRAD_V1:
+        case CLHIP_CONV_WGRAD_V1_NO_TR: break;
+        default:
+            clhip_set_error("clhip_conv_wgrad: no launch for kernel family %d", family);
+            return CLHIP_EINVAL;
     }
-    if (int e = check_conv(N, H, W, C, K, ksize, stride, pad)) return e;
-    CLHIP_CHECK_ARG(x && dz && dw && Creal >= 1 && Creal <= C);
     WgradParams p;
     p.x = x; p.dz = dz; p.dw = dw;
     p.N = N; p.H = H; p.W = W; p.C = C; p.log2C = ilog2_exact(C); p.Creal = Creal;
@@ -986,29 +1056,11 @@ extern "C" int clhip_conv_wgrad(const void* x, const void* dz, float* dw, void* 
     splits = (p.M + pps - 1) / pps;
     p.pix_per_split = pps;
     dim3 grid(gx, gy, splits);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
-    if (!use_v1() && use_v3() && ws != nullptr && clhip_stem_wgrad_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_stem_wgrad_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, Creal, K, st);
-    if (!use_v1() && use_v3() && ws != nullptr && clhip_wgrad64_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_wgrad64_launch(x, dz, dw, static_cast<float*>(ws), N, H, nullptr, st);
-    if (!use_v1() && use_v3() && ws != nullptr && clhip_wgrad4_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_wgrad4_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, C, K, ksize, stride, st);
-    if (!use_v1() && use_v3() && clhip_wgrad3_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_wgrad3_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, C, Creal, K, st);
-    if (!use_v1() && use_v3() && ws != nullptr && clhip_wgrad16_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_wgrad16_launch(x, dz, dw, static_cast<float*>(ws), N, H, nullptr, st);
-    if (!use_v1() && use_v3() && ws != nullptr && clhip_wgrad32_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype))
-        return clhip_wgrad32_launch(x, dz, dw, static_cast<float*>(ws), N, H, nullptr, st);
-    if (!use_v1()) return clhip_wgrad2_launch(x, dz, dw, static_cast<float*>(ws), N, H, W, C, Creal, K, ksize, stride, pad, dtype, st);
-    static const bool no_tr = clhip_cfg("WGRAD_NO_TR") != nullptr;
     if (dtype == CLHIP_BF16) {
-        if (no_tr) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false>), grid, dim3(256), 0, st, p);
+        if (family == CLHIP_CONV_WGRAD_V1_NO_TR) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, false>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, true>), grid, dim3(256), 0, st, p);
-    } else if (dtype == CLHIP_F32) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<float, false>), grid, dim3(256), 0, st, p);
     } else {
-        CLHIP_CHECK_ARG(!"dtype");
+        hipLaunchKernelGGL((conv_wgrad_kernel<float, false>), grid, dim3(256), 0, st, p);
     }
     CLHIP_LAUNCH_CHECK();
     return CLHIP_OK;

@@ -325,8 +325,11 @@ def test_conv8_dgrad_with_batchnorm_backward_sums(shape, accumulate, mask_from):
     try:
         assert L.clhip_config(b"CONV8_MIN_TILES", b"1") == 0
         assert L.clhip_config(b"CONV8_BNR", b"1") == 0
-        if not L.clhip_conv_dgrad_bn_reduce_overlapped(N, H, W, C, C, 3, 1, 1, code):
-            pytest.skip("layer on another kernel (small maps: conv64)")
+        # maps up to 16 wide and 32 768 pixels stay on conv3.hip's conv64 (by design: the launch is at its latency floor there): the same properties hold on it,
+        # the mask always from the activation
+        on_conv8 = W > 16
+        assert L.clhip_conv_dgrad_bn_reduce_overlapped(N, H, W, C, C, 3, 1, 1, code) == (1 if on_conv8 else 0)
+        assert L.clhip_conv_route(3, 0, N, H, W, C, C, C, 3, 1, 1, code) == (_lib.CONV_CONV8 if on_conv8 else _lib.CONV_CONV64)
         for fused in (1, 0):
             dx = to_nhwc(old, tdt).clone() if accumulate else torch.full((N, H, W, C), float("nan"), dtype=tdt, device=DEV)
             acc = torch.zeros(rep, 2, C, dtype=torch.float64, device=DEV)
@@ -365,8 +368,7 @@ def test_dgrad_and_wgrad_in_one_launch(shape, with_bn, accumulate):
     N, H, W, C = shape
     L = _lib.lib()
     code, tdt = DT["bf16"]
-    if not L.clhip_conv_dgrad_wgrad_supported(N, H, W, C, C, C, 3, 1, 1, code):
-        pytest.skip("layer outside the fused launch's domain")
+    assert L.clhip_conv_dgrad_wgrad_supported(N, H, W, C, C, C, 3, 1, 1, code) == 1
     x = to_nhwc(quant(rnd((N, C, H, W), 61), tdt), tdt)
     dz = to_nhwc(quant(rnd((N, C, H, W), 62, 0.5), tdt), tdt)
     wd = quant(rnd((C, 9, C), 63, 0.1), tdt).to(tdt).to(DEV).contiguous()
@@ -988,9 +990,28 @@ def test_dgrad_with_fused_batchnorm_backward_reduction(shape, relu, accumulate):
     fp64 math: dx, the two channel sums, dz, dgamma, dbeta, dres.  bf16 only (the fourth-generation kernel's domain); tiles that end
     inside an image, the K-split configurations (8x8, 4x4 images) and the accumulate path (dx += ...) included."""
     N, H, W, C, K = shape
+    assert _lib.lib().clhip_conv_dgrad_bn_reduce_supported(N, H, W, C, K, 3, 1, 1, DT["bf16"][0]) == 1
+    assert _lib.lib().clhip_conv_route(3, 0, N, H, W, C, C, K, 3, 1, 1, DT["bf16"][0]) != _lib.CONV_CONV9          # (off by default)
+    _bnr_case(shape, relu, accumulate)
+
+
+@pytest.mark.parametrize("shape", [(4, 8, 8, 128, 128), (3, 16, 16, 128, 128), (3, 32, 32, 128, 128), (6, 8, 8, 256, 256), (3, 16, 16, 256, 256)])
+@pytest.mark.parametrize("relu,accumulate", [(1, 0), (1, 1), (0, 0)])
+def test_dgrad_with_fused_batchnorm_backward_reduction_conv9(shape, relu, accumulate):
+    """... and the same on conv9.hip (128 -> 128 / 256 -> 256 channels, CONV9=1): tiles of four / two images, one, two and four tiles per image"""
+    N, H, W, C, K = shape
+    L = _lib.lib()
+    assert L.clhip_config(b"CONV9", b"1") == 0
+    try:
+        assert L.clhip_conv_route(3, 0, N, H, W, C, C, K, 3, 1, 1, DT["bf16"][0]) == _lib.CONV_CONV9
+        _bnr_case(shape, relu, accumulate)
+    finally:
+        L.clhip_config(b"CONV9", None)
+
+
+def _bnr_case(shape, relu, accumulate):
+    N, H, W, C, K = shape
     code, tdt = DT["bf16"]
-    if not _lib.lib().clhip_conv_dgrad_bn_reduce_supported(N, H, W, C, K, 3, 1, 1, code):
-        pytest.skip("layer outside the fused kernel's domain")
     M = N * H * W
     dzn = quant(rnd((N, K, H, W), 31, 0.5), tdt)                       # gradient entering the convolution's output
     wd = quant(rnd((C, 9, K), 32, 0.05), tdt)                          # dgrad weight copy [C][taps][K]
@@ -1138,8 +1159,11 @@ def test_lazy_batchnorm_input_forward_and_backward(shape):
     N, H, W, Cc = shape
     L = _lib.lib()
     code, tdt = DT["bf16"]
-    if not L.clhip_conv_bn_input_supported(N, H, W, Cc, Cc, 3, 1, 1, code):
-        pytest.skip("layer outside the lazy-input kernels' domain")
+    # the lazy input needs the layer's one-launch backward as well (32-wide images at 16 channels, 16-wide at 32, 8-wide at 64): (3, 7, 5, 16) is outside by design
+    inside = W == {16: 32, 32: 16, 64: 8}[Cc]
+    assert L.clhip_conv_bn_input_supported(N, H, W, Cc, Cc, 3, 1, 1, code) == (1 if inside else 0)
+    if not inside:
+        return
     M_ = N * H * W
     zp = to_nhwc(quant(rnd((N, Cc, H, W), 71, 1.3), tdt), tdt)                    # the producer's pre-BatchNorm output
     zf = zp.float().reshape(-1, Cc).double()
@@ -1280,8 +1304,11 @@ def test_lazy_batchnorm_residual_input(shape):
     N, H, W, Cc = shape
     L = _lib.lib()
     code, tdt = DT["bf16"]
-    if not L.clhip_conv_bn_input_supported(N, H, W, Cc, Cc, 3, 1, 1, code):
-        pytest.skip("layer outside the lazy-input kernels' domain")
+    # the lazy input needs the layer's one-launch backward as well (32-wide images at 16 channels, 16-wide at 32, 8-wide at 64): (3, 7, 5, 16) is outside by design
+    inside = W == {16: 32, 32: 16, 64: 8}[Cc]
+    assert L.clhip_conv_bn_input_supported(N, H, W, Cc, Cc, 3, 1, 1, code) == (1 if inside else 0)
+    if not inside:
+        return
     M_ = N * H * W
     zp = to_nhwc(quant(rnd((N, Cc, H, W), 81, 1.3), tdt), tdt)
     rs_t = to_nhwc(quant(rnd((N, Cc, H, W), 82, 0.8), tdt), tdt)                   # the residual
@@ -1338,12 +1365,20 @@ def test_lazy_batchnorm_input_write_through(shape, with_res):
     L = _lib.lib()
     code, tdt = DT["bf16"]
     assert L.clhip_config(b"BN_INPUT_WT", b"1") == 0                  # (off by default: it did not pay inside the step, profiles/r04_wt_notes.md)
+    nine = Cc == K and Cc in (128, 256)                              # conv9.hip's layers: the write-through form exists on it alone (CONV9=1; conv4.hip has no lazy input)
     try:
-        if not L.clhip_conv_bn_input_wt_supported(N, H, W, Cc, K, 3, 1, 1, code):
-            pytest.skip("layer outside the write-through lazy-input kernels' domain")
-        _wt_case(L, C, BnInput, BnRes, N, H, W, Cc, K, code, tdt, with_res)
+        if nine:
+            assert L.clhip_conv_bn_input_wt_supported(N, H, W, Cc, K, 3, 1, 1, code) == 0
+            assert L.clhip_config(b"CONV9", b"1") == 0
+            assert L.clhip_conv_route(4, 0, N, H, W, Cc, Cc, K, 3, 1, 1, code) == _lib.CONV_CONV9
+        # outside the domain by design: 512 channels and 64 -> 128 channels (conv4.hip only), 64 -> 64 below conv5.hip's 512 tiles (24 x 32 x 32: 96)
+        inside = nine or (Cc == 64 and K == 64 and N * H * W >= 512 * 256)
+        assert L.clhip_conv_bn_input_wt_supported(N, H, W, Cc, K, 3, 1, 1, code) == (1 if inside else 0)
+        if inside:
+            _wt_case(L, C, BnInput, BnRes, N, H, W, Cc, K, code, tdt, with_res)
     finally:
         L.clhip_config(b"BN_INPUT_WT", None)
+        L.clhip_config(b"CONV9", None)
 
 
 def _wt_case(L, C, BnInput, BnRes, N, H, W, Cc, K, code, tdt, with_res):
@@ -1398,6 +1433,7 @@ def _wt_case(L, C, BnInput, BnRes, N, H, W, Cc, K, code, tdt, with_res):
         coef_want = torch.stack([gamma * e["invstd"], beta - e["mean"] * (gamma * e["invstd"])])
         assert torch.allclose(l["coef"], coef_want, rtol=1e-6, atol=1e-7)
         assert ((l["acc"].sum(0) - e["acc"].sum(0)).abs() <= 1e-12 * e["acc"].sum(0).abs().clamp(min=1.0)).all()
+    return l, w          # (for tests/test_conv_routes_gpu.py: the fused launch's tensors against fp64)
 
 
 @pytest.mark.parametrize("case", [(256, 32, 32, 16, 32), (256, 16, 16, 32, 64), (5, 32, 32, 16, 32), (3, 16, 16, 32, 64), (32, 32, 32, 16, 32), (130, 16, 16, 32, 64)])
