@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 static thread_local char g_err[512] = "";
 
@@ -126,22 +126,6 @@ hipStream_t clhip_shared_stream(int role, hipStream_t main_s, bool low_priority)
     if (pick != nullptr) S.chosen[key] = pick;
     return pick;
 }
-
-// hooks that take effect at once (defined next to the kernels they steer)
-void clhip_conv4_set_cfg(int wm, int wn, int kg, int ck);
-void clhip_conv4_enable(int on);
-void clhip_conv4_set_debug(int bits);
-void clhip_conv4_set_trace(unsigned long long* dev_buf);
-void clhip_wgrad4_set_trace(unsigned long long* dev_buf);
-void clhip_conv5_enable(int on);
-void clhip_conv5_min_tiles(int n);
-void clhip_conv6_enable(int on);
-void clhip_conv8_enable(int on);
-void clhip_conv9_enable(int on);
-void clhip_conv9_set_trace(unsigned long long* dev_buf);
-void clhip_conv8_min_tiles(int n);
-void clhip_conv8_set_trace(unsigned long long* dev_buf);
-void clhip_conv6_set_trace(unsigned long long* buf, int wg);
 
 const char* clhip_cfg(const char* name) {
     {

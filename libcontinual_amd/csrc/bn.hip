@@ -9,7 +9,7 @@
 
 #include <hip/hip_ext.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -16,7 +16,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -435,69 +435,6 @@ int check_conv(int N, int H, int W, int C, int K, int ksize, int stride, int pad
 
 }  // namespace
 
-// conv2.hip
-int clhip_conv2_tiles_m(int M, int Cd);
-int clhip_conv2_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int Hs, int Ws, int Cs, int Hd, int Wd,
-                       int Cd, int ksize, int stride, int pad, int accumulate, int mode, int dtype, hipStream_t st);
-bool clhip_conv64_supported(int N, int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);      // conv3.hip
-int clhip_conv64_launch_ex(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* bn_coef,
-                           const clhip_bn_input* in, hipStream_t st, const clhip_bn_res_input* rs = nullptr);
-
-bool clhip_wgrad64_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);      // conv3.hip
-size_t clhip_wgrad64_ws_bytes(int N);
-int clhip_wgrad64_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, const float* x_coef, hipStream_t st);
-bool clhip_wgrad32_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);      // conv3.hip
-size_t clhip_wgrad32_ws_bytes(int N);
-int clhip_wgrad32_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, const float* x_coef, hipStream_t st);
-size_t clhip_wgrad2_ws_bytes(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad);
-int clhip_wgrad2_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int C, int Creal, int K, int ksize, int stride,
-                        int pad, int dtype, hipStream_t st);
-bool clhip_conv3_supported(int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);
-int clhip_conv3_tiles_m(int M, int Cd);
-int clhip_conv3_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, int accumulate,
-                       int mode, hipStream_t st);
-bool clhip_conv4_supported(int N, int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);
-int clhip_conv4_tiles_m(int M, int Cs, int Cd, int W);
-int clhip_conv4_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, int accumulate,
-                       int mode, hipStream_t st);
-int clhip_conv4_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd,
-                          int accumulate, int mode, const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep,
-                          hipStream_t st);
-bool clhip_conv16_supported(int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);
-int clhip_conv16_tiles_m(int M);
-int clhip_conv16_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                        hipStream_t st);
-bool clhip_wgrad3_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
-bool clhip_wgrad16_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
-size_t clhip_wgrad16_ws_bytes(int N);
-int clhip_wgrad16_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, const float* x_coef, hipStream_t st);
-int clhip_wgrad3_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int C, int Creal, int K, hipStream_t st);
-size_t clhip_wgrad3_ws_bytes(int N, int H, int W, int C, int K);
-bool clhip_stem_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype);
-int clhip_stem_launch(const void* x, const void* w, void* z, double* acc, int rep, int N, int H, int W, int K, hipStream_t st);
-bool clhip_stem7_supported(int N, int H, int W, int C, int K, int stride, int pad);                                   // stem7.hip (7x7 / s2 / p3)
-int clhip_stem7_fwd_tiles(int N, int H, int W);
-int clhip_stem7_fwd_launch(const void* x, const void* w, void* z, double* acc, int rep, int N, int H, int W, int K, int dtype, hipStream_t st);
-size_t clhip_stem7_wgrad_ws_bytes(int N, int H, int W, int Creal, int K, int dtype);
-int clhip_stem7_wgrad_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int Creal, int K, int dtype, hipStream_t st);
-bool clhip_shortcut_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype);
-int clhip_shortcut_dgrad(const void* dz, const void* w_dg, void* dx, int accumulate, int N, int H, int W, int C, int K, hipStream_t st);
-bool clhip_stem_wgrad_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
-size_t clhip_stem_wgrad_ws_bytes(int N, int H, int W, int Creal, int K);
-int clhip_stem_wgrad_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int Creal, int K, hipStream_t st);
-bool clhip_wgrad4_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
-size_t clhip_wgrad4_ws_bytes(int N, int H, int W, int C, int K, int ksize, int stride);
-int clhip_wgrad4_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, int W, int C, int K, int ksize, int stride, hipStream_t st);
-bool clhip_conv5_supported(int N, int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);      // conv5.hip
-int clhip_conv5_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, hipStream_t st);
-bool clhip_conv8_supported(int N, int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);      // conv8.hip
-int clhip_conv8_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, const LazyIn* in,
-                       const void* bn_z, const void* bn_y, const void* bn_mask, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_invstd,
-                       double* bn_acc, int bn_rep, hipStream_t st);
-bool clhip_conv9_supported(int N, int H, int W, int Cs, int Cd, int ksize, int stride, int pad, int dtype);      // conv9.hip
-int clhip_conv9_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode, const LazyIn* in,
-                       const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st);
 static bool use_v3() {
     static const bool v = clhip_cfg("NO_CONV3") == nullptr;    // A/B switch: halo kernel for 3x3 stride-1 layers
     return v;
@@ -532,7 +469,6 @@ extern "C" int clhip_conv_fwd_tiles(int N, int H, int W, int C, int K, int ksize
 static bool conv64_fwd_on() { const char* c = clhip_cfg("CONV64_FWD"); return !(c != nullptr && atoi(c) == 0); }
 
 static bool wgrad_v1_no_tr() { static const bool v = clhip_cfg("WGRAD_NO_TR") != nullptr; return v; }
-bool clhip_conv4_in_supported(int N, int H, int W, int Cs, int Cd);      // conv4.hip
 
 // ONE decision for clhip_conv_fwd[_acc], clhip_conv_dgrad, clhip_conv_wgrad, clhip_conv_dgrad_bn_reduce_ex, clhip_conv_fwd_acc_bn_input_wt and clhip_conv_route
 // (include/clhip.h: op, form and the CLHIP_CONV_* families): the shared argument check, then the kernels in their order of preference.  The entry
@@ -622,8 +558,8 @@ static int route_conv(int op, int form, int N, int H, int W, int C, int Creal, i
     if (clhip_conv8_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV8;
     if (clhip_conv9_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV9;
     if (clhip_conv5_supported(N, H, W, C, K, ksize, stride, pad, dtype)) return CLHIP_CONV_CONV5;
-    CLHIP_CHECK_ARG(clhip_conv4_supported(N, H, W, C, K, ksize, stride, pad, dtype) && clhip_conv4_in_supported(N, H, W, C, K));
-    return CLHIP_CONV_CONV4;
+    clhip_set_error("clhip_conv_route: no kernel with a write-through BatchNorm input for this shape (conv4.hip has none)");
+    return CLHIP_EINVAL;
 }
 
 extern "C" int clhip_conv_route(int op, int form, int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
@@ -657,6 +593,9 @@ static int conv_fwd_impl(const void* x, const void* w_fwd, void* z, float* stat_
     p.Hd = (H + 2 * pad - ksize) / stride + 1; p.Wd = (W + 2 * pad - ksize) / stride + 1; p.Cd = K;
     p.ksize = ksize; p.stride = stride; p.pad = pad; p.accumulate = 0;
     p.M = N * p.Hd * p.Wd; p.K = ksize * ksize * C;
+    ConvCall c;      // (the 3x3 / stride-1 families)
+    c.src = x; c.wt = w_fwd; c.dst = z; c.stats = stat_partials; c.stat_acc = stat_acc; c.stat_rep = stat_rep;
+    c.N = N; c.H = H; c.W = W; c.Cs = C; c.Cd = K;
     // the caller's partial buffer may hold more tiles than the kernel writes: zero the tail rows
     auto zero_tail = [&](int tiles_used) {
         const int tiles_alloc = clhip_conv_fwd_tiles(N, H, W, C, K, ksize, stride, pad);
@@ -665,21 +604,19 @@ static int conv_fwd_impl(const void* x, const void* w_fwd, void* z, float* stat_
     };
     switch (family) {
         case CLHIP_CONV_STEM: return clhip_stem_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, K, st);
-        case CLHIP_CONV_CONV64:
-            return clhip_conv64_launch_ex(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
+        case CLHIP_CONV_CONV64: return clhip_conv64_launch(c, st);
         case CLHIP_CONV_CONV16:
             zero_tail(clhip_conv16_tiles_m(p.M));
-            return clhip_conv16_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, 0, 0, st);
-        case CLHIP_CONV_CONV8:
-            return clhip_conv8_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-        case CLHIP_CONV_CONV5: return clhip_conv5_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, 0, 0, st);
-        case CLHIP_CONV_CONV9: return clhip_conv9_launch(x, w_fwd, z, stat_acc, stat_rep, N, H, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+            return clhip_conv16_launch(c, st);
+        case CLHIP_CONV_CONV8: return clhip_conv8_launch(c, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch(c, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(c, st);
         case CLHIP_CONV_CONV4:
             zero_tail(clhip_conv4_tiles_m(p.M, C, K, W));
-            return clhip_conv4_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
+            return clhip_conv4_launch(c, st);
         case CLHIP_CONV_CONV3:
             zero_tail(clhip_conv3_tiles_m(p.M, K));
-            return clhip_conv3_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, K, 0, 0, st);
+            return clhip_conv3_launch(c, st);
         case CLHIP_CONV_CONV2:
             zero_tail(clhip_conv2_tiles_m(p.M, K));
             return clhip_conv2_launch(x, w_fwd, z, stat_partials, stat_acc, stat_rep, N, H, W, C, p.Hd, p.Wd, K, ksize, stride, pad, 0, 0, dtype, st);
@@ -702,18 +639,18 @@ extern "C" int clhip_conv_dgrad(const void* dz, const void* w_dg, void* dx, int 
     p.Hd = H; p.Wd = W; p.Cd = C;
     p.ksize = ksize; p.stride = stride; p.pad = pad; p.accumulate = accumulate;
     p.M = N * H * W; p.K = ksize * ksize * K;
+    ConvCall c;      // (the 3x3 / stride-1 families: the gathered tensor is dz, K channels)
+    c.src = dz; c.wt = w_dg; c.dst = dx; c.N = N; c.H = H; c.W = W; c.Cs = K; c.Cd = C; c.accumulate = accumulate; c.mode = 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (family) {
         case CLHIP_CONV_SHORTCUT: return clhip_shortcut_dgrad(dz, w_dg, dx, accumulate, N, H, W, C, K, st);
-        case CLHIP_CONV_CONV16: return clhip_conv16_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, st);
-        case CLHIP_CONV_CONV64:
-            return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, st);
-        case CLHIP_CONV_CONV8:
-            return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-        case CLHIP_CONV_CONV5: return clhip_conv5_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, st);
-        case CLHIP_CONV_CONV9: return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-        case CLHIP_CONV_CONV4: return clhip_conv4_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
-        case CLHIP_CONV_CONV3: return clhip_conv3_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, st);
+        case CLHIP_CONV_CONV16: return clhip_conv16_launch(c, st);
+        case CLHIP_CONV_CONV64: return clhip_conv64_launch(c, st);
+        case CLHIP_CONV_CONV8: return clhip_conv8_launch(c, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch(c, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(c, st);
+        case CLHIP_CONV_CONV4: return clhip_conv4_launch(c, st);
+        case CLHIP_CONV_CONV3: return clhip_conv3_launch(c, st);
         case CLHIP_CONV_CONV2: return clhip_conv2_launch(dz, w_dg, dx, nullptr, nullptr, 1, N, p.Hs, p.Ws, K, H, W, C, ksize, stride, pad, accumulate, 1, dtype, st);
         case CLHIP_CONV_V1: return dtype == CLHIP_BF16 ? launch_igemm<bf16_t, 1>(p, st) : launch_igemm<float, 1>(p, st);
         default: break;
@@ -721,9 +658,6 @@ extern "C" int clhip_conv_dgrad(const void* dz, const void* w_dg, void* dx, int 
     clhip_set_error("clhip_conv_dgrad: no launch for kernel family %d", family);
     return CLHIP_EINVAL;
 }
-
-int clhip_conv16_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st);      // conv3.hip
 
 extern "C" int clhip_conv_dgrad_bn_reduce_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype) {
     return route_conv(OP_DGRAD_BNR, 0, N, H, W, C, C, K, ksize, stride, pad, dtype) > 0 ? 1 : 0;
@@ -755,28 +689,23 @@ extern "C" int clhip_conv_dgrad_bn_reduce_ex(const void* dz, const void* w_dg, v
     if (family < 0) return family;
     CLHIP_CHECK_ARG(dz && w_dg && dx && z_prod && mean && invstd && acc);
     CLHIP_CHECK_ARG(replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0);
+    BnSums b;
+    b.z = z_prod; b.y = y_prod; b.mean = mean; b.invstd = invstd; b.acc = acc; b.rep = replicas;
+    if (family == CLHIP_CONV_CONV8) { b.mask = mask_prod; b.gamma = gamma_prod; b.beta = beta_prod; }      // (the cheaper mask sources: the other kernels fall back to y_prod)
+    ConvCall c;
+    c.src = dz; c.wt = w_dg; c.dst = dx; c.N = N; c.H = H; c.W = W; c.Cs = K; c.Cd = C; c.accumulate = accumulate; c.mode = 1; c.bnr = &b;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (family) {
-        case CLHIP_CONV_CONV64:
-            return clhip_conv64_launch_ex(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, nullptr, nullptr, st);
-        case CLHIP_CONV_CONV16: return clhip_conv16_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, st);
-        case CLHIP_CONV_CONV8:
-            return clhip_conv8_launch(dz, w_dg, dx, nullptr, 1, N, H, W, accumulate, 1, nullptr, z_prod, y_prod, mask_prod, gamma_prod, beta_prod, mean, invstd, acc, replicas, st);
-        case CLHIP_CONV_CONV9: return clhip_conv9_launch(dz, w_dg, dx, nullptr, 1, N, H, W, C, accumulate, 1, nullptr, z_prod, y_prod, mean, invstd, acc, replicas, st);
-        case CLHIP_CONV_CONV4: return clhip_conv4_launch_bn(dz, w_dg, dx, nullptr, nullptr, 1, N, H, W, K, C, accumulate, 1, z_prod, y_prod, mean, invstd, acc, replicas, st);
+        case CLHIP_CONV_CONV64: return clhip_conv64_launch(c, st);
+        case CLHIP_CONV_CONV16: return clhip_conv16_launch(c, st);
+        case CLHIP_CONV_CONV8: return clhip_conv8_launch(c, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(c, st);
+        case CLHIP_CONV_CONV4: return clhip_conv4_launch(c, st);
         default: break;
     }
     clhip_set_error("clhip_conv_dgrad_bn_reduce: no launch for kernel family %d", family);
     return CLHIP_EINVAL;
 }
-
-bool clhip_bwd_fused_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);      // conv3.hip
-int clhip_bwd_fused_launch(const void* x, const void* dz, const void* w_dg, void* dx, int accumulate, float* dw, float* ws, int N, int H, int W, int C,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* x_coef,
-                           const clhip_bn_grad* lz, hipStream_t st);
-int clhip_conv16_launch_ex(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* bn_coef,
-                           const clhip_bn_input* in, hipStream_t st, const clhip_bn_res_input* rs = nullptr);
 
 // ---- "lazy" BatchNorm input: the consumer applies relu(bn(z)) of its producer while it stages its operand (conv3.hip conv16 / conv32: the
 //      kernels that stage through registers); the producer's apply launch and activation tensor do not exist
@@ -816,20 +745,13 @@ static int conv_fwd_acc_bn_input(const void* z_in, const clhip_bn_input* bn, con
         CLHIP_CHECK_ARG((bn->running_mean == nullptr) == (bn->running_var == nullptr));
     }
     CLHIP_CHECK_ARG(clhip_conv_bn_input_supported(N, H, W, C, K, ksize, stride, pad, dtype));
-    if (C == 64)
-        return clhip_conv64_launch_ex(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, bn,
-                                      static_cast<hipStream_t>(stream), rs);
-    return clhip_conv16_launch_ex(z_in, w_fwd, z, nullptr, stat_acc, replicas, N, H, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, bn,
-                                  static_cast<hipStream_t>(stream), rs);
+    ConvCall c;
+    c.src = z_in; c.wt = w_fwd; c.dst = z; c.stat_acc = stat_acc; c.stat_rep = replicas; c.N = N; c.H = H; c.W = W; c.Cs = C; c.Cd = K; c.bn_in = bn; c.rs = rs;
+    return C == 64 ? clhip_conv64_launch(c, static_cast<hipStream_t>(stream)) : clhip_conv16_launch(c, static_cast<hipStream_t>(stream));
 }
 
 // ---- the same for the LDS-DMA kernels of the wide layers (conv5.hip: 64 -> 64 channels at >= 512 tiles; conv4.hip: C, K multiples of 64): the
 //      transform happens IN LDS on the landed patch and the launch always writes the activation (common.h LazyIn)
-int clhip_conv5_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, const LazyIn* in,
-                          hipStream_t st);
-bool clhip_conv4_in_supported(int N, int H, int W, int Cs, int Cd);
-int clhip_conv4_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, const LazyIn* in, hipStream_t st);
-
 extern "C" int clhip_conv_bn_input_wt_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype) {
     return route_conv(OP_FWD_WT, 0, N, H, W, C, C, K, ksize, stride, pad, dtype) > 0 ? 1 : 0;      // (why it is off by default: route_conv)
 }
@@ -848,13 +770,13 @@ extern "C" int clhip_conv_fwd_acc_bn_input_wt(const void* z_in, const clhip_bn_i
     const double M = (double)N * H * W;
     in.invM = 1.0 / M; in.unbias = M > 1.0 ? M / (M - 1.0) : 1.0;
     in.res = static_cast<const bf16_t*>(rs->res); in.y = static_cast<bf16_t*>(rs->y); in.mask = static_cast<unsigned char*>(rs->relu_mask);
+    ConvCall c;
+    c.src = z_in; c.wt = w_fwd; c.dst = z; c.stat_acc = stat_acc; c.stat_rep = replicas; c.N = N; c.H = H; c.W = W; c.Cs = C; c.Cd = K; c.in = &in;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (family) {
-        case CLHIP_CONV_CONV8:
-            return clhip_conv8_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-        case CLHIP_CONV_CONV9: return clhip_conv9_launch(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, 0, 0, &in, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-        case CLHIP_CONV_CONV5: return clhip_conv5_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, 0, 0, &in, st);
-        case CLHIP_CONV_CONV4: return clhip_conv4_launch_in(z_in, w_fwd, z, stat_acc, replicas, N, H, W, C, K, &in, st);
+        case CLHIP_CONV_CONV8: return clhip_conv8_launch(c, st);
+        case CLHIP_CONV_CONV9: return clhip_conv9_launch(c, st);
+        case CLHIP_CONV_CONV5: return clhip_conv5_launch(c, st);
         default: break;
     }
     clhip_set_error("clhip_conv_fwd_acc_bn_input_wt: no launch for kernel family %d", family);
@@ -868,8 +790,9 @@ extern "C" int clhip_conv_dgrad_wgrad_bn_input(const void* x_z, const float* x_c
     CLHIP_CHECK_ARG(x_z && x_coef && dz && w_dg && dx && dw && ws);
     CLHIP_CHECK_ARG(clhip_conv_bn_input_supported(N, H, W, C, K, ksize, stride, pad, dtype) && Creal == C);
     CLHIP_CHECK_ARG(acc == nullptr || (mean && invstd && replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0));
-    return clhip_bwd_fused_launch(x_z, dz, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, acc ? x_z : nullptr, nullptr, mean, invstd, acc, replicas,
-                                  x_coef, nullptr, static_cast<hipStream_t>(stream));
+    BnSums b;      // (a lazy x IS the producer's z)
+    b.z = acc ? x_z : nullptr; b.mean = mean; b.invstd = invstd; b.acc = acc; b.rep = replicas;
+    return clhip_bwd_fused_launch(x_z, dz, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, b, x_coef, nullptr, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int clhip_conv_dgrad_wgrad_bn_grad(const void* x, const float* x_coef, const clhip_bn_grad* bn, const void* w_dg, void* dx, int accumulate, float* dw, void* ws,
@@ -881,8 +804,9 @@ extern "C" int clhip_conv_dgrad_wgrad_bn_grad(const void* x, const float* x_coef
     CLHIP_CHECK_ARG(clhip_conv_bn_input_supported(N, H, W, C, K, ksize, stride, pad, dtype) && Creal == C);
     CLHIP_CHECK_ARG(z_prod == nullptr || (mean && invstd && acc && replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0));
     CLHIP_CHECK_ARG(bn->relu_mask != nullptr || bn->dres == nullptr);          // a residual gradient only exists behind a masked (+res) layer
-    return clhip_bwd_fused_launch(x, nullptr, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, x_coef != nullptr ? (z_prod ? x : nullptr) : z_prod,
-                                  x_coef != nullptr ? nullptr : y_prod, mean, invstd, acc, replicas, x_coef, bn, static_cast<hipStream_t>(stream));
+    BnSums b;
+    b.z = x_coef != nullptr ? (z_prod ? x : nullptr) : z_prod; b.y = x_coef != nullptr ? nullptr : y_prod; b.mean = mean; b.invstd = invstd; b.acc = acc; b.rep = replicas;
+    return clhip_bwd_fused_launch(x, nullptr, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, b, x_coef, bn, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int clhip_conv_dgrad_wgrad_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
@@ -898,22 +822,12 @@ extern "C" int clhip_conv_dgrad_wgrad(const void* x, const void* dz, const void*
     CLHIP_CHECK_ARG(x && dz && w_dg && dx && dw && ws);
     CLHIP_CHECK_ARG(clhip_conv_dgrad_wgrad_supported(N, H, W, C, Creal, K, ksize, stride, pad, dtype));
     CLHIP_CHECK_ARG(z_prod == nullptr || (mean && invstd && acc && replicas >= 1 && replicas <= 64 && (replicas & (replicas - 1)) == 0));
-    return clhip_bwd_fused_launch(x, dz, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, z_prod, y_prod, mean, invstd, acc, replicas, nullptr,
-                                  nullptr, static_cast<hipStream_t>(stream));
+    BnSums b;
+    b.z = z_prod; b.y = y_prod; b.mean = mean; b.invstd = invstd; b.acc = acc; b.rep = replicas;
+    return clhip_bwd_fused_launch(x, dz, w_dg, dx, accumulate, dw, static_cast<float*>(ws), N, H, W, C, b, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
-bool clhip_dgrad6_supported(int N, int H, int W, int C, int K, int dtype);      // conv6.hip
-size_t clhip_dgrad6_packed_bytes(int C, int K);
-int clhip_dgrad6_pack(const void* w_dg, const void* w_sc_dg, void* packed, int C, int K, hipStream_t st);
-int clhip_dgrad6_launch(const void* dz, const void* w_packed, const void* dz_sc, void* dx, int accumulate, int N, int H, int W, int C, int K, hipStream_t st);
-
-// conv7.hip: the same for 16 -> 32 and 32 -> 64 channels (CifarResNet-32), packed [C][10][K]
-bool clhip_dgrad7_supported(int N, int H, int W, int C, int K, int dtype);
-size_t clhip_dgrad7_packed_bytes(int C, int K);
-int clhip_dgrad7_pack(const void* w_dg, const void* w_sc_dg, void* packed, int C, int K, hipStream_t st);
-int clhip_dgrad7_launch(const void* dz, const void* w_packed, const void* dz_sc, void* dx, int accumulate, int N, int H, int W, int C, int K, hipStream_t st,
-                        const void* bn_z = nullptr, const void* bn_y = nullptr, const float* bn_mean = nullptr, const float* bn_invstd = nullptr, double* bn_acc = nullptr,
-                        int bn_rep = 1);
+// the input gradient of a down-sampling block entry in one launch: conv6.hip, and conv7.hip for 16 -> 32 and 32 -> 64 channels (CifarResNet-32)
 static bool small_pair(int C, int K) { return (C == 16 || C == 32) && K == 2 * C; }
 
 extern "C" int clhip_conv_dgrad_pair_supported(int N, int H, int W, int C, int K, int dtype) {
@@ -942,17 +856,10 @@ extern "C" int clhip_conv_dgrad_pair(const void* dz, const void* w_packed, const
     return clhip_dgrad6_launch(dz, w_packed, dz_sc, dx, accumulate, N, H, W, C, K, static_cast<hipStream_t>(stream));
 }
 
-// conv7.hip: the weight gradients of a small-channel down-sampling entry (3x3/s2 + 1x1/s2 shortcut) in one launch
-bool clhip_wgrad7_supported(int N, int H, int W, int C, int K, int dtype);
-size_t clhip_wgrad7_ws_bytes(int N, int C, int K, int which);
-int clhip_wgrad7_launch(const void* x, const void* dz, const void* dz_sc, float* dw, float* dw_sc, float* ws3, float* ws_sc, int N, int C, hipStream_t st);
 static size_t wgrad_ws_bytes_single(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
 
-bool clhip_fwd7_supported(int N, int H, int W, int C, int K, int dtype);
-int clhip_fwd7_launch(const void* x, const void* w3, const void* wsc, void* z3, void* zsc, double* acc3, int rep3, double* accsc, int repsc, int N, int H, int W, int C,
-                      hipStream_t st);
-
-// ... and their two FORWARD convolutions with the BatchNorm statistics of both (clhip_conv_fwd_acc twice) from one pass over x
+// conv7.hip: the two FORWARD convolutions of a small-channel down-sampling entry (3x3/s2 + 1x1/s2 shortcut) with the BatchNorm statistics of both
+// (clhip_conv_fwd_acc twice) from one pass over x
 extern "C" int clhip_conv_fwd_acc_pair_supported(int N, int H, int W, int C, int K, int dtype) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || use_v1() || !use_v3()) return 0;
     return clhip_fwd7_supported(N, H, W, C, K, dtype) ? 1 : 0;
@@ -966,6 +873,7 @@ extern "C" int clhip_conv_fwd_acc_pair(const void* x, const void* w_fwd, const v
     return clhip_fwd7_launch(x, w_fwd, w_sc_fwd, z, z_sc, stat_acc, replicas, stat_acc_sc, replicas_sc, N, H, W, C, static_cast<hipStream_t>(stream));
 }
 
+// ... and its two weight gradients in one launch
 extern "C" int clhip_conv_wgrad_pair_supported(int N, int H, int W, int C, int K, int dtype) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || use_v1() || !use_v3()) return 0;
     return clhip_wgrad7_supported(N, H, W, C, K, dtype) ? 1 : 0;

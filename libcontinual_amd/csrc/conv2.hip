@@ -14,9 +14,7 @@
 //   * workgroup shapes chosen per layer so that >= 2 workgroups per CU exist even for the 4x4 / 8x8 layers.
 #include <stdlib.h>
 
-#include "common.h"
-
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);      // conv3.hip
+#include "kernels.h"
 
 namespace {
 

@@ -13,7 +13,7 @@
 // Orientation, MFMA shape, swizzle, epilogue (bf16 store + BatchNorm partial statistics) as in conv2.hip.
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -1193,51 +1193,46 @@ bool clhip_conv16_supported(int H, int W, int Cs, int Cd, int ksize, int stride,
 
 int clhip_conv16_tiles_m(int M) { return (M + 255) / 256; }
 
-int clhip_conv16_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st);
-int clhip_conv16_launch_ex(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* bn_coef,
-                           const clhip_bn_input* in, hipStream_t st, const clhip_bn_res_input* rs = nullptr);
-
-int clhip_conv16_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                        hipStream_t st) {
-    return clhip_conv16_launch_bn(src, wt, dst, stats, stat_acc, stat_rep, N, H, W, C, accumulate, mode, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
+// the optional groups of a ConvCall into the kernel parameters: the sums of the dgrad epilogue ...
+static void set_bn_sums3(Conv3Params& p, const BnSums& b) {
+    p.bn_coef = b.coef;
+    p.bn_z = static_cast<const bf16_t*>(b.z); p.bn_y = static_cast<const bf16_t*>(b.y); p.bn_mean = b.mean; p.bn_invstd = b.invstd;
+    p.bn_acc = b.acc; p.bn_rep = b.rep > 0 ? b.rep : 1;
 }
-
-int clhip_conv16_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st) {
-    return clhip_conv16_launch_ex(src, wt, dst, stats, stat_acc, stat_rep, N, H, W, C, accumulate, mode, bn_z, bn_y, bn_mean, bn_invstd, bn_acc, bn_rep, nullptr, nullptr, st);
-}
-
-// bn_coef: the dgrad epilogue's ReLU mask from z (bn_y == nullptr); in: forward with a lazy BatchNorm input (src = the producer's z)
-int clhip_conv16_launch_ex(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* bn_coef,
-                           const clhip_bn_input* in, hipStream_t st, const clhip_bn_res_input* rs) {
-    Conv3Params p;
-    p.bn_coef = bn_coef;
+// ... and the lazy BatchNorm input of a forward over M pixels (src = the producer's z)
+static void set_lazy_in3(Conv3Params& p, const clhip_bn_input* in, const clhip_bn_res_input* rs, double M) {
     if (rs != nullptr) { p.in_res = static_cast<const bf16_t*>(rs->res); p.in_y = static_cast<bf16_t*>(rs->y); p.in_mask = static_cast<unsigned char*>(rs->relu_mask); }
     if (in != nullptr) {
         p.in_acc = in->stat_acc; p.in_eval = in->stat_acc == nullptr ? 1 : 0; p.in_rep = in->replicas; p.in_gamma = in->gamma; p.in_beta = in->beta; p.in_rm = in->running_mean; p.in_rv = in->running_var;
         p.in_momentum = in->momentum; p.in_eps = in->eps; p.in_mean_o = in->mean; p.in_invstd_o = in->invstd; p.in_coef_o = in->coef;
-        const double M = (double)N * H * W;
         p.in_invM = 1.0 / M; p.in_unbias = M > 1.0 ? M / (M - 1.0) : 1.0;
     }
-    p.bn_z = static_cast<const bf16_t*>(bn_z); p.bn_y = static_cast<const bf16_t*>(bn_y); p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-    p.bn_acc = bn_acc; p.bn_rep = bn_rep > 0 ? bn_rep : 1;
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stats = stats; p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1;
-    p.N = N; p.H = H; p.W = W; p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(H); p.Cs = C; p.Cd = C; p.accumulate = accumulate; p.M = N * H * W;
+}
+// src / wt / dst, the statistics and the geometry
+static void set_call3(Conv3Params& p, const ConvCall& c) {
+    p.src = static_cast<const bf16_t*>(c.src); p.wt = static_cast<const bf16_t*>(c.wt); p.dst = static_cast<bf16_t*>(c.dst);
+    p.stats = c.stats; p.stat_acc = c.stat_acc; p.stat_rep = c.stat_rep > 0 ? c.stat_rep : 1;
+    p.N = c.N; p.H = c.H; p.W = c.W; p.wshift = ilog2_exact(c.W); p.hshift = ilog2_exact(c.H); p.Cs = c.Cs; p.Cd = c.Cd; p.accumulate = c.accumulate; p.M = c.N * c.H * c.W;
+}
+
+int clhip_conv16_launch(const ConvCall& c, hipStream_t st) {
+    CLHIP_CHECK_ARG(c.Cs == c.Cd && c.in == nullptr && (c.rs == nullptr || c.bn_in != nullptr) && !(c.bnr && (c.bnr->mask || c.bnr->gamma || c.bnr->beta)));
+    const int C = c.Cs, W = c.W, mode = c.mode;
+    Conv3Params p;
+    if (c.bnr != nullptr) set_bn_sums3(p, *c.bnr);
+    set_lazy_in3(p, c.bn_in, c.rs, (double)c.N * c.H * c.W);
+    set_call3(p, c);
     p.np = 256 + 2 * W + 2; p.patch_bytes = (p.np + 1) * (C == 16 ? 32 : 96); p.nbuf = 1; p.debug = 0;
     const size_t lds = ((size_t)p.patch_bytes > 1024 ? (size_t)p.patch_bytes : 1024) + 1024;      // + the lazy operands' coefficient tables ([2][C] / [6][C])
     const dim3 grid(clhip_conv16_tiles_m(p.M));
     if (C == 16) {
-        if (mode == 0 && in != nullptr && rs != nullptr) hipLaunchKernelGGL((conv16_kernel<0, 2>), grid, dim3(256), lds, st, p);
-        else if (mode == 0 && in != nullptr) hipLaunchKernelGGL((conv16_kernel<0, 1>), grid, dim3(256), lds, st, p);
+        if (mode == 0 && c.bn_in != nullptr && c.rs != nullptr) hipLaunchKernelGGL((conv16_kernel<0, 2>), grid, dim3(256), lds, st, p);
+        else if (mode == 0 && c.bn_in != nullptr) hipLaunchKernelGGL((conv16_kernel<0, 1>), grid, dim3(256), lds, st, p);
         else if (mode == 0) hipLaunchKernelGGL(conv16_kernel<0>, grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL(conv16_kernel<1>, grid, dim3(256), lds, st, p);
     } else {
-        if (mode == 0 && in != nullptr && rs != nullptr) hipLaunchKernelGGL((conv32_kernel<0, 2>), grid, dim3(256), lds, st, p);
-        else if (mode == 0 && in != nullptr) hipLaunchKernelGGL((conv32_kernel<0, 1>), grid, dim3(256), lds, st, p);
+        if (mode == 0 && c.bn_in != nullptr && c.rs != nullptr) hipLaunchKernelGGL((conv32_kernel<0, 2>), grid, dim3(256), lds, st, p);
+        else if (mode == 0 && c.bn_in != nullptr) hipLaunchKernelGGL((conv32_kernel<0, 1>), grid, dim3(256), lds, st, p);
         else if (mode == 0) hipLaunchKernelGGL(conv32_kernel<0>, grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL(conv32_kernel<1>, grid, dim3(256), lds, st, p);
     }
@@ -1253,36 +1248,26 @@ bool clhip_conv64_supported(int N, int H, int W, int Cs, int Cd, int ksize, int 
     return !off && dtype == CLHIP_BF16 && ksize == 3 && stride == 1 && pad == 1 && Cs == 64 && Cd == 64 && W <= max_w && W >= 2 && H >= 1 && (int64_t)N * H * W <= max_m;
 }
 
-int clhip_conv64_launch_ex(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* bn_coef,
-                           const clhip_bn_input* in, hipStream_t st, const clhip_bn_res_input* rs) {
+int clhip_conv64_launch(const ConvCall& c, hipStream_t st) {
+    CLHIP_CHECK_ARG(c.Cs == 64 && c.Cd == 64 && c.stats == nullptr && c.in == nullptr && (c.rs == nullptr || c.bn_in != nullptr) && !(c.bnr && (c.bnr->mask || c.bnr->gamma || c.bnr->beta)));
+    const int W = c.W, mode = c.mode;
     Conv3Params p;
-    p.bn_coef = bn_coef;
-    if (rs != nullptr) { p.in_res = static_cast<const bf16_t*>(rs->res); p.in_y = static_cast<bf16_t*>(rs->y); p.in_mask = static_cast<unsigned char*>(rs->relu_mask); }
-    if (in != nullptr) {
-        p.in_acc = in->stat_acc; p.in_eval = in->stat_acc == nullptr ? 1 : 0; p.in_rep = in->replicas; p.in_gamma = in->gamma; p.in_beta = in->beta; p.in_rm = in->running_mean; p.in_rv = in->running_var;
-        p.in_momentum = in->momentum; p.in_eps = in->eps; p.in_mean_o = in->mean; p.in_invstd_o = in->invstd; p.in_coef_o = in->coef;
-        const double M = (double)N * H * W;
-        p.in_invM = 1.0 / M; p.in_unbias = M > 1.0 ? M / (M - 1.0) : 1.0;
-    }
-    p.bn_z = static_cast<const bf16_t*>(bn_z); p.bn_y = static_cast<const bf16_t*>(bn_y); p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-    p.bn_acc = bn_acc; p.bn_rep = bn_rep > 0 ? bn_rep : 1;
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stats = nullptr; p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1;
-    p.N = N; p.H = H; p.W = W; p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(H); p.Cs = 64; p.Cd = 64; p.accumulate = accumulate; p.M = N * H * W;
+    if (c.bnr != nullptr) set_bn_sums3(p, *c.bnr);
+    set_lazy_in3(p, c.bn_in, c.rs, (double)c.N * c.H * c.W);
+    set_call3(p, c);
     static const int bm_cfg = clhip_cfg("CONV64_BM") ? atoi(clhip_cfg("CONV64_BM")) : 64;       // (128-pixel tiles measured equal on ResNet-32 stage 3)
     const int bm = (bm_cfg == 128 && p.M >= 128 * 128) ? 128 : 64;       // 128-pixel tiles while they still give every second CU a workgroup
     p.np = bm + 2 * W + 2; p.patch_bytes = (p.np + 1) * 144; p.nbuf = 1; p.debug = 0;
     const size_t lds = (size_t)p.patch_bytes + 2048;
     const dim3 grid((p.M + bm - 1) / bm);
     if (bm == 128) {
-        if (mode == 0 && in != nullptr && rs != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 2, 128>), grid, dim3(256), lds, st, p);
-        else if (mode == 0 && in != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 1, 128>), grid, dim3(256), lds, st, p);
+        if (mode == 0 && c.bn_in != nullptr && c.rs != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 2, 128>), grid, dim3(256), lds, st, p);
+        else if (mode == 0 && c.bn_in != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 1, 128>), grid, dim3(256), lds, st, p);
         else if (mode == 0) hipLaunchKernelGGL((conv64_kernel<0, 0, 128>), grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL((conv64_kernel<1, 0, 128>), grid, dim3(256), lds, st, p);
     } else {
-        if (mode == 0 && in != nullptr && rs != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 2>), grid, dim3(256), lds, st, p);
-        else if (mode == 0 && in != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 1>), grid, dim3(256), lds, st, p);
+        if (mode == 0 && c.bn_in != nullptr && c.rs != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 2>), grid, dim3(256), lds, st, p);
+        else if (mode == 0 && c.bn_in != nullptr) hipLaunchKernelGGL((conv64_kernel<0, 1>), grid, dim3(256), lds, st, p);
         else if (mode == 0) hipLaunchKernelGGL(conv64_kernel<0>, grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL(conv64_kernel<1>, grid, dim3(256), lds, st, p);
     }
@@ -1296,22 +1281,22 @@ bool clhip_conv3_supported(int H, int W, int Cs, int Cd, int ksize, int stride, 
 
 int clhip_conv3_tiles_m(int M, int Cd) { return (M + pick3(M, Cd).wm * 64 - 1) / (pick3(M, Cd).wm * 64); }
 
-int clhip_conv3_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, int accumulate,
-                       int mode, hipStream_t st) {
+int clhip_conv3_launch(const ConvCall& c, hipStream_t st) {
+    CLHIP_CHECK_ARG(c.in == nullptr && c.bn_in == nullptr && c.rs == nullptr && c.bnr == nullptr);
+    const int Cd = c.Cd, mode = c.mode;
     Conv3Params p;
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stats = stats; p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1; p.N = N; p.H = H; p.W = W; p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(H); p.Cs = Cs; p.Cd = Cd; p.accumulate = accumulate; p.M = N * H * W;
+    set_call3(p, c);
     static const int dbg = clhip_cfg("CONV3_DEBUG") ? atoi(clhip_cfg("CONV3_DEBUG")) : 0;
     p.debug = dbg;
-    Cfg3 c = pick3(p.M, Cd);
+    Cfg3 g = pick3(p.M, Cd);
 #define L3(a, b) (mode == 0 ? launch3<a, b, 0>(p, st) : launch3<a, b, 1>(p, st))
-    if (c.wn == 1) {
-        if (c.wm == 8) return L3(8, 1);
-        if (c.wm == 4) return L3(4, 1);
+    if (g.wn == 1) {
+        if (g.wm == 8) return L3(8, 1);
+        if (g.wm == 4) return L3(4, 1);
         return L3(2, 1);
     }
-    if (c.wm == 4) return L3(4, 2);
-    if (c.wm == 2) return L3(2, 2);
+    if (g.wm == 4) return L3(4, 2);
+    if (g.wm == 2) return L3(2, 2);
     return L3(1, 2);
 #undef L3
 }
@@ -1863,8 +1848,6 @@ bool clhip_wgrad32_supported(int N, int H, int W, int C, int Creal, int K, int k
 
 size_t clhip_wgrad32_ws_bytes(int N) { return (size_t)wgrad32_groups(N) * 9216 * sizeof(float); }
 
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);
-
 int clhip_wgrad32_launch(const void* x, const void* dz, float* dw, float* ws, int N, int H, const float* x_coef, hipStream_t st) {
     const int groups = wgrad32_groups(N);
     Wgrad32Params p{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(dz), ws, N, H, (N + groups - 1) / groups, x_coef};
@@ -2004,8 +1987,8 @@ bool clhip_bwd_fused_supported(int N, int H, int W, int C, int Creal, int K, int
 }
 
 int clhip_bwd_fused_launch(const void* x, const void* dz, const void* w_dg, void* dx, int accumulate, float* dw, float* ws, int N, int H, int W, int C,
-                           const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, const float* x_coef,
-                           const clhip_bn_grad* lz, hipStream_t st) {
+                           const BnSums& bnr, const float* x_coef, const clhip_bn_grad* lz, hipStream_t st) {
+    CLHIP_CHECK_ARG(bnr.mask == nullptr && bnr.gamma == nullptr && bnr.beta == nullptr && bnr.coef == nullptr);
     Conv3Params pd;
     LazyDz lzd;
     if (lz != nullptr) {                                     // dz = the layer's own BatchNorm backward, computed on both bodies' operand loads
@@ -2015,9 +1998,8 @@ int clhip_bwd_fused_launch(const void* x, const void* dz, const void* w_dg, void
         lzd.invM = 1.0 / ((double)N * H * W);
     }
     pd.lz = lzd;
-    pd.bn_coef = x_coef;                                     // a lazy x IS the producer's z: its ReLU mask comes from z as well (bn_y is NULL then)
-    pd.bn_z = static_cast<const bf16_t*>(bn_z); pd.bn_y = static_cast<const bf16_t*>(bn_y); pd.bn_mean = bn_mean; pd.bn_invstd = bn_invstd;
-    pd.bn_acc = bn_acc; pd.bn_rep = bn_rep > 0 ? bn_rep : 1;
+    set_bn_sums3(pd, bnr);
+    pd.bn_coef = x_coef;                                     // a lazy x IS the producer's z: its ReLU mask comes from z as well (bnr.y is NULL then)
     pd.src = static_cast<const bf16_t*>(dz); pd.wt = static_cast<const bf16_t*>(w_dg); pd.dst = static_cast<bf16_t*>(dx);
     pd.stats = nullptr; pd.stat_acc = nullptr; pd.stat_rep = 1;
     pd.N = N; pd.H = H; pd.W = W; pd.wshift = ilog2_exact(W); pd.hshift = ilog2_exact(H); pd.Cs = C; pd.Cd = C; pd.accumulate = accumulate; pd.M = N * H * W;

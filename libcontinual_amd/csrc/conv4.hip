@@ -29,7 +29,7 @@
 // (core/model/backbone/resnet.py:17-24, 295-298, 337, 367).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -617,30 +617,23 @@ bool clhip_conv4_supported(int N, int H, int W, int Cs, int Cd, int ksize, int s
 
 int clhip_conv4_tiles_m(int M, int Cs, int Cd, int W) { return (M + pick4(M, Cs, Cd, W).wm * 64 - 1) / (pick4(M, Cs, Cd, W).wm * 64); }
 
-int clhip_conv4_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd,
-                          int accumulate, int mode, const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep,
-                          hipStream_t st);
-
-int clhip_conv4_launch(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd,
-                       int accumulate, int mode, hipStream_t st) {
-    return clhip_conv4_launch_bn(src, wt, dst, stats, stat_acc, stat_rep, N, H, W, Cs, Cd, accumulate, mode, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st);
-}
-
-int clhip_conv4_launch_bn(const void* src, const void* wt, void* dst, float* stats, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd,
-                          int accumulate, int mode, const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep,
-                          hipStream_t st) {
+// (no lazy BatchNorm input, common.h LazyIn: not built for this kernel family)
+int clhip_conv4_launch(const ConvCall& c, hipStream_t st) {
+    const BnSums none, &b = c.bnr ? *c.bnr : none;
+    CLHIP_CHECK_ARG(c.in == nullptr && c.bn_in == nullptr && c.rs == nullptr && !(b.mask || b.gamma || b.beta || b.coef));
+    const int W = c.W, Cs = c.Cs, Cd = c.Cd, mode = c.mode;
     Conv4Params p;
-    p.bn_z = static_cast<const bf16_t*>(bn_z); p.bn_y = static_cast<const bf16_t*>(bn_y); p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-    p.bn_acc = bn_acc; p.bn_rep = bn_rep > 0 ? bn_rep : 1;
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stats = stats; p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1;
-    p.H = H; p.W = W; p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(H); p.Cs = Cs; p.Cd = Cd; p.accumulate = accumulate; p.M = N * H * W;
+    p.bn_z = static_cast<const bf16_t*>(b.z); p.bn_y = static_cast<const bf16_t*>(b.y); p.bn_mean = b.mean; p.bn_invstd = b.invstd;
+    p.bn_acc = b.acc; p.bn_rep = b.rep > 0 ? b.rep : 1;
+    p.src = static_cast<const bf16_t*>(c.src); p.wt = static_cast<const bf16_t*>(c.wt); p.dst = static_cast<bf16_t*>(c.dst);
+    p.stats = c.stats; p.stat_acc = c.stat_acc; p.stat_rep = c.stat_rep > 0 ? c.stat_rep : 1;
+    p.H = c.H; p.W = W; p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(c.H); p.Cs = Cs; p.Cd = Cd; p.accumulate = c.accumulate; p.M = c.N * c.H * W;
     p.debug = g_debug4; p.trace = g_trace4;
-    Cfg4 c = pick4(p.M, Cs, Cd, W);
-    if (!cfg_ok(c, Cs, Cd)) { clhip_set_error("conv4: configuration %d,%d,%d,%d does not fit Cs=%d Cd=%d", c.wm, c.wn, c.kg, c.ck, Cs, Cd); return CLHIP_EINVAL; }
+    Cfg4 g = pick4(p.M, Cs, Cd, W);
+    if (!cfg_ok(g, Cs, Cd)) { clhip_set_error("conv4: configuration %d,%d,%d,%d does not fit Cs=%d Cd=%d", g.wm, g.wn, g.kg, g.ck, Cs, Cd); return CLHIP_EINVAL; }
 #define L4(a, b, g, k) (W <= 8 ? (mode == 0 ? launch4<a, b, g, k, 8, 0>(p, st) : launch4<a, b, g, k, 8, 1>(p, st)) \
                                : (mode == 0 ? launch4<a, b, g, k, 32, 0>(p, st) : launch4<a, b, g, k, 32, 1>(p, st)))
-    const int key = c.wm * 1000 + c.wn * 100 + c.kg * 10 + (c.ck == 64 ? 1 : 0);
+    const int key = g.wm * 1000 + g.wn * 100 + g.kg * 10 + (g.ck == 64 ? 1 : 0);
     switch (key) {
         case 4110: return L4(4, 1, 1, 32);
         case 4111: return L4(4, 1, 1, 64);
@@ -662,7 +655,7 @@ int clhip_conv4_launch_bn(const void* src, const void* wt, void* dst, float* sta
         default: break;
     }
 #undef L4
-    clhip_set_error("conv4: no kernel for configuration %d,%d,%d,%d", c.wm, c.wn, c.kg, c.ck);
+    clhip_set_error("conv4: no kernel for configuration %d,%d,%d,%d", g.wm, g.wn, g.kg, g.ck);
     return CLHIP_EINVAL;
 }
 
@@ -671,11 +664,3 @@ void clhip_conv4_set_cfg(int wm, int wn, int kg, int ck) { g_force4[0] = wm; g_f
 void clhip_conv4_enable(int on) { g_enable4 = on; }
 void clhip_conv4_set_debug(int bits) { g_debug4 = bits; }
 void clhip_conv4_set_trace(unsigned long long* dev_buf) { g_trace4 = dev_buf; }
-
-// ---- lazy BatchNorm input (common.h LazyIn): not built for this kernel family yet
-bool clhip_conv4_in_supported(int N, int H, int W, int Cs, int Cd) { (void)N; (void)H; (void)W; (void)Cs; (void)Cd; return false; }
-int clhip_conv4_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int Cs, int Cd, const LazyIn* in, hipStream_t st) {
-    (void)src; (void)wt; (void)dst; (void)stat_acc; (void)stat_rep; (void)N; (void)H; (void)W; (void)Cs; (void)Cd; (void)in; (void)st;
-    clhip_set_error("conv4: lazy inputs are not supported");
-    return CLHIP_EINVAL;
-}

@@ -20,7 +20,7 @@
 // nn.Conv2d forward / input gradient of the 64-channel 3x3 layers (core/model/backbone/resnet.py:17-24, 295-298: ResNet-18 layer1).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -403,26 +403,19 @@ void clhip_conv5_min_tiles(int n) { g_min_tiles5 = n; }
 
 int clhip_conv5_tiles_m(int M) { return (M + BM5 - 1) / BM5; }
 
-int clhip_conv5_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, const LazyIn* in,
-                          hipStream_t st);
-
-int clhip_conv5_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, hipStream_t st) {
-    return clhip_conv5_launch_in(src, wt, dst, stat_acc, stat_rep, N, H, W, accumulate, mode, nullptr, st);
-}
-
-// in != nullptr (forward only): src is the producer's pre-BatchNorm output, the operand relu(bn(src) [+ in->res]) is formed in LDS and written to in->y
-int clhip_conv5_launch_in(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, const LazyIn* in,
-                          hipStream_t st) {
+int clhip_conv5_launch(const ConvCall& c, hipStream_t st) {
+    CLHIP_CHECK_ARG(c.Cs == C5 && c.Cd == C5 && c.stats == nullptr && c.bn_in == nullptr && c.rs == nullptr && c.bnr == nullptr);
+    const int H = c.H, W = c.W, mode = c.mode;
     Conv5Params p;
-    if (in != nullptr) {
-        if (mode != 0 || in->acc == nullptr || in->y == nullptr) { clhip_set_error("conv5: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
-        p.in = *in;
+    if (c.in != nullptr) {
+        if (mode != 0 || c.in->acc == nullptr || c.in->y == nullptr) { clhip_set_error("conv5: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
+        p.in = *c.in;
     }
     static const int wt_debug = clhip_cfg("WT_DEBUG") ? atoi(clhip_cfg("WT_DEBUG")) : 0;
     p.in_debug = wt_debug;
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1;
-    p.H = H; p.W = W; p.M = N * H * W; p.accumulate = accumulate;
+    p.src = static_cast<const bf16_t*>(c.src); p.wt = static_cast<const bf16_t*>(c.wt); p.dst = static_cast<bf16_t*>(c.dst);
+    p.stat_acc = c.stat_acc; p.stat_rep = c.stat_rep > 0 ? c.stat_rep : 1;
+    p.H = H; p.W = W; p.M = c.N * H * W; p.accumulate = c.accumulate;
     p.wshift = ilog2_exact(W); p.hshift = ilog2_exact(H);
     p.np = BM5 + 2 * W + 2;
     p.zoff = (p.np * PP5 + 255) / 256 * 256;
@@ -430,7 +423,7 @@ int clhip_conv5_launch_in(const void* src, const void* wt, void* dst, double* st
     p.patch_bytes = pinst * 4 * 1024;
     p.n_tiles = (p.M + BM5 - 1) / BM5;
     if (p.zoff + 512 > p.patch_bytes) { clhip_set_error("conv5: patch geometry"); return CLHIP_EINVAL; }
-#define L5(PI) (mode == 0 ? (in == nullptr ? launch5<0, PI>(p, st) : (in->res != nullptr ? launch5<0, PI, 2>(p, st) : launch5<0, PI, 1>(p, st))) : launch5<1, PI>(p, st))
+#define L5(PI) (mode == 0 ? (c.in == nullptr ? launch5<0, PI>(p, st) : (c.in->res != nullptr ? launch5<0, PI, 2>(p, st) : launch5<0, PI, 1>(p, st))) : launch5<1, PI>(p, st))
     switch (pinst) {
         case 10: return L5(10);
         case 11: return L5(11);

@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 

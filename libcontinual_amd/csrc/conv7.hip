@@ -14,7 +14,7 @@
 // layout in its own weight preparation, clhip_conv_dgrad_pair_pack makes it from the two copies.
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -293,8 +293,6 @@ template <int C> int wgrad7_groups(int N) { const int ipg = C == 16 ? (N >= 256 
 template <int C> int wgrad7_ipg(int N) { return C == 16 ? (N >= 256 ? N / 128 : 1) : (N >= 128 ? N / 64 : 1); }
 
 }  // namespace
-
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);      // conv3.hip
 
 // (N, H, W, C) = the block input; K = 2 C.  CifarResNet-32's two entries: 32 x 32 x 16 and 16 x 16 x 32
 bool clhip_wgrad7_supported(int N, int H, int W, int C, int K, int dtype) {

@@ -24,7 +24,7 @@
 // (resnet.py:37-63).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -533,29 +533,28 @@ void clhip_conv8_min_tiles(int n) { g_min_tiles8 = n; }
 void clhip_conv8_set_trace(unsigned long long* dev_buf) { g_trace8 = dev_buf; }
 int clhip_conv8_tiles_m(int M) { return (M + BM8 - 1) / BM8; }
 
-// mode 0: forward (stat_acc may be nullptr); mode 1: dgrad, with the producer's BatchNorm-backward sums when bn_z != nullptr.
-// in != nullptr (forward only): src is the producer's pre-BatchNorm output, the operand relu(bn(src) [+ in->res]) is formed in LDS and written to in->y
-int clhip_conv8_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int accumulate, int mode, const LazyIn* in,
-                       const void* bn_z, const void* bn_y, const void* bn_mask, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_invstd,
-                       double* bn_acc, int bn_rep, hipStream_t st) {
+int clhip_conv8_launch(const ConvCall& c, hipStream_t st) {
+    const BnSums none, &b = c.bnr ? *c.bnr : none;
+    CLHIP_CHECK_ARG(c.Cs == C8 && c.Cd == C8 && c.stats == nullptr && c.bn_in == nullptr && c.rs == nullptr && b.coef == nullptr);
+    const int N = c.N, H = c.H, W = c.W, mode = c.mode;
     Conv8Params p;
-    p.bn_gamma = bn_gamma; p.bn_beta = bn_gamma != nullptr ? bn_beta : nullptr;
+    p.bn_gamma = b.gamma; p.bn_beta = b.gamma != nullptr ? b.beta : nullptr;
     if (!geometry8(N, H, W, p)) { clhip_set_error("conv8: unsupported geometry %d x %d x %d", N, H, W); return CLHIP_EINVAL; }
-    if (in != nullptr) {
-        if (mode != 0 || in->acc == nullptr || in->y == nullptr) { clhip_set_error("conv8: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
-        p.in = *in;
+    if (c.in != nullptr) {
+        if (mode != 0 || c.in->acc == nullptr || c.in->y == nullptr) { clhip_set_error("conv8: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
+        p.in = *c.in;
     }
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1; p.accumulate = accumulate;
-    p.bn_z = static_cast<const bf16_t*>(bn_z); p.bn_y = static_cast<const bf16_t*>(bn_y); p.bn_mask = static_cast<const unsigned char*>(bn_mask);
-    p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_acc = bn_acc; p.bn_rep = bn_rep > 0 ? bn_rep : 1;
+    p.src = static_cast<const bf16_t*>(c.src); p.wt = static_cast<const bf16_t*>(c.wt); p.dst = static_cast<bf16_t*>(c.dst);
+    p.stat_acc = c.stat_acc; p.stat_rep = c.stat_rep > 0 ? c.stat_rep : 1; p.accumulate = c.accumulate;
+    p.bn_z = static_cast<const bf16_t*>(b.z); p.bn_y = static_cast<const bf16_t*>(b.y); p.bn_mask = static_cast<const unsigned char*>(b.mask);
+    p.bn_mean = b.mean; p.bn_invstd = b.invstd; p.bn_acc = b.acc; p.bn_rep = b.rep > 0 ? b.rep : 1;
     p.trace = g_trace8;
     if (mode == 0) {
-        if (in == nullptr) return launch8<0, 0, 0>(p, st);
-        return in->res != nullptr ? launch8<0, 2, 0>(p, st) : launch8<0, 1, 0>(p, st);
+        if (c.in == nullptr) return launch8<0, 0, 0>(p, st);
+        return c.in->res != nullptr ? launch8<0, 2, 0>(p, st) : launch8<0, 1, 0>(p, st);
     }
-    if (bn_z == nullptr) return launch8<1, 0, 0>(p, st);
-    if (bn_mask != nullptr) return launch8<1, 0, 1>(p, st);
-    if (bn_gamma != nullptr) return launch8<1, 0, 2>(p, st);
-    return bn_y != nullptr ? launch8<1, 0, 3>(p, st) : launch8<1, 0, 4>(p, st);
+    if (b.z == nullptr) return launch8<1, 0, 0>(p, st);
+    if (b.mask != nullptr) return launch8<1, 0, 1>(p, st);
+    if (b.gamma != nullptr) return launch8<1, 0, 2>(p, st);
+    return b.y != nullptr ? launch8<1, 0, 3>(p, st) : launch8<1, 0, 4>(p, st);
 }

@@ -22,7 +22,7 @@
 // and the BatchNorm + ReLU (+ residual) in front of them (resnet.py:37-63).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -503,28 +503,28 @@ void clhip_conv9_enable(int on) { g_enable9 = on; }
 void clhip_conv9_set_trace(unsigned long long* dev_buf) { g_trace9 = dev_buf; }
 int clhip_conv9_tiles_m(int N, int H, int W, int C) { Conv9Params p; return geometry9(N, H, W, C, p) ? p.n_mtiles : 0; }
 
-// mode 0: forward (stat_acc may be nullptr); mode 1: dgrad, with the producer's BatchNorm-backward sums when bn_z != nullptr.
-// in != nullptr (forward only): src is the producer's pre-BatchNorm output, the operand relu(bn(src) [+ in->res]) is formed in LDS and written to in->y
-int clhip_conv9_launch(const void* src, const void* wt, void* dst, double* stat_acc, int stat_rep, int N, int H, int W, int C, int accumulate, int mode, const LazyIn* in,
-                       const void* bn_z, const void* bn_y, const float* bn_mean, const float* bn_invstd, double* bn_acc, int bn_rep, hipStream_t st) {
+int clhip_conv9_launch(const ConvCall& c, hipStream_t st) {
+    const BnSums none, &b = c.bnr ? *c.bnr : none;
+    CLHIP_CHECK_ARG(c.Cs == c.Cd && c.stats == nullptr && c.bn_in == nullptr && c.rs == nullptr && !(b.mask || b.gamma || b.beta || b.coef));
+    const int N = c.N, H = c.H, W = c.W, C = c.Cs, mode = c.mode;
     Conv9Params p;
     if (!geometry9(N, H, W, C, p)) { clhip_set_error("conv9: unsupported geometry %d x %d x %d x %d", N, H, W, C); return CLHIP_EINVAL; }
-    if (in != nullptr) {
-        if (mode != 0 || in->acc == nullptr || in->y == nullptr) { clhip_set_error("conv9: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
-        p.in = *in;
+    if (c.in != nullptr) {
+        if (mode != 0 || c.in->acc == nullptr || c.in->y == nullptr) { clhip_set_error("conv9: a lazy input needs the forward mode, the producer's sums and an output activation"); return CLHIP_EINVAL; }
+        p.in = *c.in;
     }
-    p.src = static_cast<const bf16_t*>(src); p.wt = static_cast<const bf16_t*>(wt); p.dst = static_cast<bf16_t*>(dst);
-    p.stat_acc = stat_acc; p.stat_rep = stat_rep > 0 ? stat_rep : 1; p.accumulate = accumulate;
-    p.bn_z = static_cast<const bf16_t*>(bn_z); p.bn_y = static_cast<const bf16_t*>(bn_y);
-    p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_acc = bn_acc; p.bn_rep = bn_rep > 0 ? bn_rep : 1;
+    p.src = static_cast<const bf16_t*>(c.src); p.wt = static_cast<const bf16_t*>(c.wt); p.dst = static_cast<bf16_t*>(c.dst);
+    p.stat_acc = c.stat_acc; p.stat_rep = c.stat_rep > 0 ? c.stat_rep : 1; p.accumulate = c.accumulate;
+    p.bn_z = static_cast<const bf16_t*>(b.z); p.bn_y = static_cast<const bf16_t*>(b.y);
+    p.bn_mean = b.mean; p.bn_invstd = b.invstd; p.bn_acc = b.acc; p.bn_rep = b.rep > 0 ? b.rep : 1;
     p.trace = g_trace9;
 #define L9(CC)                                                                                                      \
     do {                                                                                                            \
         if (mode == 0) {                                                                                            \
-            if (in == nullptr) return launch9<CC, 0, 0, false>(p, st);                                              \
-            return in->res != nullptr ? launch9<CC, 0, 2, false>(p, st) : launch9<CC, 0, 1, false>(p, st);          \
+            if (c.in == nullptr) return launch9<CC, 0, 0, false>(p, st);                                              \
+            return c.in->res != nullptr ? launch9<CC, 0, 2, false>(p, st) : launch9<CC, 0, 1, false>(p, st);          \
         }                                                                                                           \
-        return bn_z != nullptr ? launch9<CC, 1, 0, true>(p, st) : launch9<CC, 1, 0, false>(p, st);                  \
+        return b.z != nullptr ? launch9<CC, 1, 0, true>(p, st) : launch9<CC, 1, 0, false>(p, st);                   \
     } while (0)
     if (C == 128) L9(128);
     L9(256);

@@ -16,12 +16,7 @@
 
 #include <mutex>
 
-#include "common.h"
-
-// gemm8.hip
-int clhip_gemm8_rows(int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldh, int dtype);
-int clhip_gemm8_launch(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
-                       int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, hipStream_t st);
+#include "kernels.h"
 
 namespace {
 

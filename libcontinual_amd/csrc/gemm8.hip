@@ -31,7 +31,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -14,15 +14,7 @@
 #include <vector>
 #include <new>
 
-#include "common.h"
-
-void clhip_bn_set_stop_event(hipEvent_t ev);          // bn.hip: one-shot completion event of the next accumulator-path backward apply launch
-hipEvent_t clhip_bn_pending_stop_event();
-void clhip_bn_set_fwd_stop_event(hipEvent_t ev);      // ... of the next accumulator-path forward apply launch
-void clhip_wgrad_defer_begin();                        // conv3.hip: collect the partial-block reduces of the weight-gradient launches ...
-int clhip_wgrad_defer_flush(hipStream_t st, bool end);  // ... and run them as one launch
-void clhip_wgrad_defer_abort();
-void clhip_wgrad_defer_pause(bool paused);
+#include "kernels.h"
 
 namespace {
 constexpr float kBnMomentum = 0.1f;   // nn.BatchNorm2d defaults used by every reference ResNet
@@ -37,24 +29,6 @@ struct Act {
     size_t bytes;
 };
 
-}  // namespace
-bool clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype);                                                   // stage.hip
-int clhip_stage_eval_launch(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
-                            const float* const* mean, const float* const* var, float eps, int dtype, hipStream_t st);
-bool clhip_stage_train_supported(int N, int H, int W, int C, int nconv, int dtype);                                            // stage_train.hip
-size_t clhip_stage_train_xch_bytes(int N);
-bool clhip_stage_train_xcd_rule(bool probe);
-int clhip_stage_train_fwd_launch(const void* x, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
-                                 float* const* rm, float* const* rv, float* const* mean, float* const* invstd, float* const* coef, void* const* z, void* const* y,
-                                 void* const* mask, float momentum, float eps, void* xch, int trace, int entry, float* feat, int dtype, hipStream_t st);
-int clhip_stage_train_bwd_launch(const void* x, const void* dy, void* dx, int dx_accumulate, int N, int H, int W, int C, int nconv, const void* const* wd,
-                                 const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* invstd, const void* const* z,
-                                 const void* const* y, float* const* dgamma, float* const* dbeta, float* const* slab, void* const* dzg, void* xch, int trace, int entry, const float* dfeat, int dtype, hipStream_t st);
-int clhip_stage_train_slab_blocks(int N, int C);
-int clhip_stage_train_trace(void* xch, unsigned long long* out24);
-int clhip_stage_train_status(void* xch);
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);                                // conv3.hip
-namespace {
 struct Unit {
     clhip_unit_desc d;
     int cin_pad;

@@ -13,7 +13,7 @@
 // than through the generic kernel and stay there (profiles/r02_layer_roofline.md).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 

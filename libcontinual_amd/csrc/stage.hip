@@ -14,7 +14,7 @@
 //  * the pre-BatchNorm value is rounded to bf16 first, as the unfused path stores it, so the two paths differ by summation order only.
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 

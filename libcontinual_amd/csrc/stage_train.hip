@@ -14,7 +14,7 @@
 //    backward recomputes it from z, as the per-unit "lazy" path does).  Either backward can therefore follow either forward.
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 #include "xch.h"
 
 namespace {

@@ -12,7 +12,7 @@
 //    accumulators like conv4.hip).
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -213,8 +213,6 @@ int stem_wgrad_grid(int M) {
 }
 
 }  // namespace
-
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);      // conv3.hip
 
 bool clhip_stem_wgrad_supported(int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype) {
     static const bool off = clhip_cfg("NO_STEM") != nullptr;

@@ -19,7 +19,7 @@
 //    applies the ReLU mask (recomputed from z with the forward's scale / shift) and accumulates the two BatchNorm-backward sums.
 #include <stdlib.h>
 
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -449,8 +449,6 @@ int pool_blocks(int64_t nchunks) {
 bool pool_c_ok(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
 
 }  // namespace
-
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);      // conv3.hip
 
 // ------------------------------------------------------------------------------------------------ entries (conv.hip routes ksize 7 here)
 bool clhip_stem7_supported(int N, int H, int W, int C, int K, int stride, int pad) {

@@ -26,9 +26,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "common.h"
-
-int clhip_wgrad_reduce_launch(const float* slab, float* dw, int64_t n4, int splits, hipStream_t st);      // conv3.hip
+#include "kernels.h"
 
 namespace {
 

@@ -112,8 +112,8 @@ FAMILY_NAMES = {STEM7: "stem7", STEM: "stem", CONV64: "conv64", CONV16: "conv16"
                 CONV2: "conv2", V1: "v1-igemm", SHORTCUT: "shortcut", W_STEM7: "wgrad-stem7", W_STEM: "wgrad-stem", W64: "wgrad64", W4: "wgrad4", W3: "wgrad3",
                 W16: "wgrad16", W32: "wgrad32", W2_DET: "wgrad2-deterministic", W2_ATOMIC: "wgrad2-atomic", W_V1: "wgrad-v1", W_V1_NO_TR: "wgrad-v1-no-transpose"}
 OP_FWD, OP_DGRAD, OP_WGRAD, OP_BNR, OP_WT = 0, 1, 2, 3, 4
-# the families each dispatcher names.  The write-through forward (op 4) names conv4 as well, but clhip_conv4_in_supported is a stub that answers no: no shape
-# reaches it (tests/test_conv_ref_cpu.py asserts the refusal)
+# the families each dispatcher names.  The write-through forward (op 4) does not name conv4: conv4.hip has no lazy input, and a shape that only it would serve
+# is refused (tests/test_conv_ref_cpu.py asserts the refusal)
 FAMILIES = {
     OP_FWD: {STEM7, STEM, CONV64, CONV16, CONV8, CONV5, CONV9, CONV4, CONV3, CONV2, V1},
     OP_DGRAD: {SHORTCUT, CONV16, CONV64, CONV8, CONV5, CONV9, CONV4, CONV3, CONV2, V1},
