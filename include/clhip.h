@@ -595,6 +595,27 @@ int clhip_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, 
 /* dqkv [B*N, 3D] from dout [B*N, D]; dsum_ws: [B,H,N] floats (only used by the generic fp32 path) */
 int clhip_attn_bwd(const void* qkv, const void* out, const float* lse, const void* dout, void* dqkv, float* dsum_ws, int B, int N,
                    int H, int D, int dtype, void* stream);
+/* Prefix-tuning attention: MultiHeadAttention.forward with `prompt` given (transformer.py:175-180: k = cat(pk, k), v = cat(pv, v) per sample and head).
+ * qkv, out, lse, dout, dqkv exactly as in clhip_attn_fwd / _bwd; pk, pv [B, Lp, D] in the compute dtype (column = head*d + i): per-sample key and value
+ * rows that have no query.  Per (batch, head) the N token queries attend over the Lp + N keys [prefix | tokens].  dpk, dpv [B, Lp, D] fp32 are WRITTEN
+ * (not accumulated); deterministic, no atomics.  1 <= Lp, N + Lp <= 256, d <= 64; anything else is CLHIP_EINVAL.  csrc/attn_prefix.hip. */
+int clhip_attn_prefix_fwd(const void* qkv, const void* pk, const void* pv, void* out, float* lse, int B, int N, int Lp, int H, int D, int dtype, void* stream);
+int clhip_attn_prefix_bwd(const void* qkv, const void* pk, const void* pv, const void* out, const float* lse, const void* dout, void* dqkv, float* dpk,
+                          float* dpv, float* dsum_ws, int B, int N, int Lp, int H, int D, int dtype, void* stream);
+/* CODA-Prompt's prompt assembly, CodaPrompt.forward (prompt.py:158-220) for `layers` prompted layers in one launch, exact fp32.  K, A, P, ek, ev, dpk, dpv,
+ * dK, dA, dP: HOST arrays of `layers` device pointers.  Per layer K, A [pool, D], P [pool, L, D] (fp32 masters), q [B, D] fp32 (shared by the layers).
+ * fwd: c[l,b,k] = <q_b * A_k, K_k> / (max(|q_b * A_k|, 1e-12) max(|K_k|, 1e-12)) for k < f (prompt.py:190-194), kept as c [layers, B, f] fp32;
+ *      P_[b] = sum_{k<f} c[b,k] P[k] (prompt.py:196); rows [0, L/2) -> ek [B, L/2, D], rows [L/2, L) -> ev (prompt.py:199-201), compute dtype:
+ *      the pk / pv of clhip_attn_prefix_fwd.
+ * bwd: from dpk, dpv [B, L/2, D] fp32 writes rows [s, f) of dK, dA [pool, D] and dP [pool, L, D] (the components the running task trains,
+ *      prompt.py:174-182) and nothing outside them; q gets no gradient; the batch is summed in order (bit-reproducible).  ws: clhip_coda_ws_bytes.
+ * D % 64 == 0, L even, 1 <= f <= pool, 0 <= s < f. */
+size_t clhip_coda_ws_bytes(int layers, int B, int s, int f);
+int clhip_coda_fwd(int layers, const float* q, const float* const* K, const float* const* A, const float* const* P, void* const* ek, void* const* ev, float* c,
+                   int B, int D, int pool, int L, int f, int dtype, void* stream);
+int clhip_coda_bwd(int layers, const float* q, const float* const* K, const float* const* A, const float* const* P, const float* c, const float* const* dpk,
+                   const float* const* dpv, float* const* dK, float* const* dA, float* const* dP, float* ws, int B, int D, int pool, int L, int s, int f,
+                   void* stream);
 /* nn.LayerNorm over the last dim (transformer.py:1331-1336): y = (x-mean)*rstd*gamma+beta; mean/rstd [M] saved when given */
 int clhip_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps,
                  int dtype, void* stream);
@@ -737,6 +758,18 @@ int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, const float
 int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream);
 int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
                               float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream);
+/* Prefix mode of the executor (VisionTransformer.forward with `prompt`, transformer.py:2272-2288: blocks whose prompt is not None attend over
+ * [prefix | tokens]).  New entry points; descriptors and parameter tables are untouched.
+ * set_prefix: Lp [depth] (host, copied; 0 = a plain layer, at least one > 0), pk / pv [depth] host arrays of device pointers to [B, Lp[l], D] in the
+ *          compute dtype (copied; the BUFFERS are the caller's and must outlive the backward).  The state PERSISTS: every forward after it runs in prefix
+ *          mode until Lp == NULL switches it off (CODA-Prompt's query pass runs with the mode off).  A forward remembers the prefixes it ran with, so
+ *          switching afterwards does not disturb its backward.  The saved lse stays [B, H, N]; the workspace size does not change.
+ * backward_prefix: clhip_vit_backward of a forward that ran in prefix mode (required for one, refused otherwise); also fills dpk / dpv = [depth] host
+ *          arrays of fp32 [B, Lp[l], D] buffers (entries of plain layers are ignored).  Without other gradients the chain stops at the lowest
+ *          prefixed layer's attention backward. */
+int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* const* pk, const void* const* pv);
+int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                              float* const* d_lora_b, float* const* dpk, float* const* dpv, void* stream);
 /* debug/test: copy one saved activation of layer l (0 x_in, 1 qkv, 2 attn out, 3 x_mid, 4 GELU derivative of the mlp) to fp32 */
 int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream);
 

@@ -174,6 +174,11 @@ _PROTOS = {
     "clhip_wgrad4_config": (None, [_i]),
     "clhip_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "clhip_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "clhip_attn_prefix_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "clhip_attn_prefix_bwd": (_i, [_p] * 10 + [_i] * 6 + [_p]),
+    "clhip_coda_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "clhip_coda_fwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "clhip_coda_bwd": (_i, [_i] + [_p] * 11 + [_i] * 6 + [_p]),
     "clhip_ln_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p]),
     "clhip_ln_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "clhip_ln_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
@@ -212,6 +217,8 @@ _PROTOS = {
     "clhip_vit_set_sdlora": (_i, [_p, _i, _p, _p, _p, _p]),
     "clhip_vit_sdlora_refresh": (_i, [_p, C.POINTER(VitParams), _p, _p]),
     "clhip_vit_backward_sdlora": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
+    "clhip_vit_set_prefix": (_i, [_p, _p, _p, _p]),
+    "clhip_vit_backward_prefix": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),

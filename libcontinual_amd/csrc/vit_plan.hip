@@ -22,6 +22,8 @@ struct Layout {          // byte offsets into the workspace for one (B, n_prompt
     int B, P, N, M, save;
     size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, g2, ad_dh, ad_ws, sd_ws, total;
     std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse, ad_hd;   // per layer (x_in has depth+1 entries)
+    std::vector<int> pf_lp;                  // prefix mode of the forward that filled this layout (empty = off): per layer the prefix length ...
+    std::vector<const void*> pf_pk, pf_pv;   // ... and the caller's key / value rows, which the backward reads again
 };
 
 template <typename T>
@@ -46,6 +48,8 @@ struct clhip_vit {
     std::vector<int> sd_ranks;
     const float* const* sd_factors;        // ... and the caller's device tables
     const float *sd_mag, *sd_inv;
+    std::vector<int> pf_lp;                // prefix mode (clhip_vit_set_prefix): per layer the prefix length (empty = off) ...
+    std::vector<const void*> pf_pk, pf_pv; // ... and the caller's buffers
 };
 
 // `flags`: bit 0 = keep what the backward needs; bit 1 (CLHIP_VIT_KEEP_ATTN_IN) = keep every layer's attention input (LN1 output) until the
@@ -186,6 +190,21 @@ extern "C" int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, 
     return CLHIP_OK;
 }
 
+extern "C" int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* const* pk, const void* const* pv) {
+    CLHIP_CHECK_ARG(v != nullptr);
+    if (Lp == nullptr) { v->pf_lp.clear(); v->pf_pk.clear(); v->pf_pv.clear(); return CLHIP_OK; }
+    CLHIP_CHECK_ARG(pk && pv);
+    const int n = v->d.depth;
+    bool any = false;
+    for (int l = 0; l < n; ++l) {
+        CLHIP_CHECK_ARG(Lp[l] >= 0 && Lp[l] < 256 && (Lp[l] == 0 || (pk[l] && pv[l])));
+        any = any || Lp[l] > 0;
+    }
+    CLHIP_CHECK_ARG(any);
+    v->pf_lp.assign(Lp, Lp + n); v->pf_pk.assign(pk, pk + n); v->pf_pv.assign(pv, pv + n);
+    return CLHIP_OK;
+}
+
 extern "C" int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && v->sd_terms > 0);
     char* sh = static_cast<char*>(shadow);
@@ -237,6 +256,7 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
     const clhip_vit_desc& d = v->d;
     Layout& L = v->last;
     make_layout(v, B, n_prompt, (save ? 1 : 0) | (gram ? 2 : 0), L);
+    L.pf_lp = v->pf_lp; L.pf_pk = v->pf_pk; L.pf_pv = v->pf_pv;                  // (make_layout leaves them alone: the mode of THIS forward)
     v->have_last = true;
     char* ws = static_cast<char*>(workspace);
     const char* sh = static_cast<const char*>(shadow);
@@ -258,7 +278,11 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
         char* h1 = ws + L.h1[l];
         TRY(clhip_ln_fwd(ws + L.x_in[l], p.ln1_w, p.ln1_b, h1, st1, st1 + M, M, D, beps, dt, stream));
         TRY(clhip_gemm_nt(h1, sh + s.qkv_f, ws + L.qkv[l], p.qkv_b, nullptr, nullptr, M, 3 * D, D, D, D, 3 * D, 0, 0, EPI_BIAS, dt, stream));
-        TRY(clhip_attn_fwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<float*>(ws + L.lse[l]), B, N, d.heads, D, dt, stream));
+        if (!L.pf_lp.empty() && L.pf_lp[l] > 0)
+            TRY(clhip_attn_prefix_fwd(ws + L.qkv[l], L.pf_pk[l], L.pf_pv[l], ws + L.attn_o[l], reinterpret_cast<float*>(ws + L.lse[l]), B, N, L.pf_lp[l], d.heads, D,
+                                      dt, stream));
+        else
+            TRY(clhip_attn_fwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<float*>(ws + L.lse[l]), B, N, d.heads, D, dt, stream));
         TRY(clhip_gemm_nt(ws + L.attn_o[l], sh + s.proj_f, ws + L.x_mid[l], p.proj_b, ws + L.x_in[l], nullptr, M, D, D, D, D, D, D, 0, EPI_BIAS_RES, dt, stream));
         TRY(clhip_ln_fwd(ws + L.x_mid[l], p.ln2_w, p.ln2_b, ws + L.ln_out, st2, st2 + M, M, D, beps, dt, stream));
         TRY(clhip_gemm_nt(ws + L.ln_out, sh + s.fc1_f, ws + L.act, p.fc1_b, nullptr, save ? ws + L.hpre[l] : nullptr, M, Hm, D, D, D, Hm, 0, Hm, EPI_BIAS_GELU, dt,
@@ -286,23 +310,30 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
 }
 
 static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, void* stream);
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream);
 
 extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                                           float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream) {
-    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, d_adapter, nullptr, nullptr, stream);
+    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, d_adapter, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                                          float* dprompt_tokens, float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream) {
     CLHIP_CHECK_ARG(v && v->sd_terms > 0 && d_factors && d_mag_rows && d_mag);
-    TRY(backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, d_factors, d_mag_rows, stream));
+    TRY(backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, d_factors, d_mag_rows, nullptr, nullptr, stream));
     return clhip_sdlora_mag_reduce(d_mag_rows, v->d.depth, v->sd_terms, d_mag, stream);
 }
 
-// d_sd (nullable): the SD-LoRA gradients, run where the lora_B gradients run (the two modes exclude each other)
+extern "C" int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                                         float* const* d_lora_b, float* const* dpk, float* const* dpv, void* stream) {
+    CLHIP_CHECK_ARG(v && dpk && dpv);
+    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, nullptr, nullptr, dpk, dpv, stream);
+}
+
+// d_sd (nullable): the SD-LoRA gradients, run where the lora_B gradients run (the two modes exclude each other).  dpk / dpv: the prefix gradients of a forward
+// that ran in prefix mode (required then, refused otherwise)
 static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, void* stream) {
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && dfeat);
     CLHIP_CHECK_ARG(d_sd == nullptr || (v->sd_terms > 0 && d_lora_b == nullptr && v->last.sd_ws != 0));
     CLHIP_CHECK_ARG(d_adapter == nullptr || v->d.adapter_dim > 0);
@@ -311,6 +342,10 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
     const Layout& L = v->last;
     CLHIP_CHECK_ARG(dprompt_tokens == nullptr || L.P > 0);
     CLHIP_CHECK_ARG(d_lora_b == nullptr || d.lora_rank > 0);
+    CLHIP_CHECK_ARG((dpk != nullptr) == !L.pf_lp.empty() && (dpk != nullptr) == (dpv != nullptr));
+    int lowest = 0;                                            // the lowest layer whose attention backward somebody needs
+    if (dpk && !dprompt_tokens && !d_lora_b && !d_adapter && !d_sd)
+        while (L.pf_lp[lowest] == 0) ++lowest;
     char* ws = static_cast<char*>(workspace);
     const char* sh = static_cast<const char*>(shadow);
     const int D = d.dim, Hm = d.mlp, M = L.M, N = L.N, B = L.B, dt = v->dtype;
@@ -369,8 +404,13 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
         // attention branch: x_mid = x_in + proj(attn(qkv(LN1(x_in))))
         TRY(clhip_gemm_nt(g, sh + s.proj_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, D, D, D, D, 0, 0, EPI_NONE, dt, stream));
         if (lora_pending) { (void)hipStreamWaitEvent(main_s, v->ev_l, 0); lora_pending = false; }     // the previous layer's dB has read dqkv
-        TRY(clhip_attn_bwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<const float*>(ws + L.lse[l]), ws + L.dtmp, ws + L.dqkv,
-                           reinterpret_cast<float*>(ws + L.dsum), B, N, d.heads, D, dt, stream));
+        if (dpk && L.pf_lp[l] > 0) {
+            CLHIP_CHECK_ARG(dpk[l] && dpv[l]);
+            TRY(clhip_attn_prefix_bwd(ws + L.qkv[l], L.pf_pk[l], L.pf_pv[l], ws + L.attn_o[l], reinterpret_cast<const float*>(ws + L.lse[l]), ws + L.dtmp,
+                                      ws + L.dqkv, dpk[l], dpv[l], reinterpret_cast<float*>(ws + L.dsum), B, N, L.pf_lp[l], d.heads, D, dt, stream));
+        } else
+            TRY(clhip_attn_bwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<const float*>(ws + L.lse[l]), ws + L.dtmp, ws + L.dqkv,
+                               reinterpret_cast<float*>(ws + L.dsum), B, N, d.heads, D, dt, stream));
         if (d_lora_b) {
             CLHIP_CHECK_ARG(p.lora_a_k && p.lora_a_v && d_lora_b[2 * l] && d_lora_b[2 * l + 1]);
             TRY(leaf([&](void* ls) {
@@ -387,7 +427,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
                                          D, dt, ls);
             }));
         }
-        if (l == 0 && dprompt_tokens == nullptr) break;           // nothing below the first block needs a gradient
+        if (l == lowest && dprompt_tokens == nullptr) break;      // nothing below the first block (or the lowest prefixed one) needs a gradient
         TRY(clhip_gemm_nt(ws + L.dqkv, sh + s.qkv_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, 3 * D, 3 * D, 3 * D, D, 0, 0, EPI_NONE, dt, stream));
         TRY(clhip_ln_bwd(ws + L.dtmp, ws + L.x_in[l], p.ln1_w, st1, st1 + M, g, M, D, dt, stream));
     }

@@ -10,6 +10,7 @@ kwargs and plugin code written against it keep working:
     MultiHeadAttention_LoRA    transformer.py:199-274   (apply_lora, init_param, merge_weight, reset_input_matrix, cur_matrix)
     MultiHeadAttention_SDLoRA  transformer.py:276-357   (lora_{A,B}_{q,v}_list, mag_lora, assimilated_mag_lora_{q,v}, init_param)
     L2PPrompt                  core/model/backbone/prompt.py:345-406 (prompt, prompt_key)
+    CodaPromptPool             core/model/backbone/prompt.py:37-223  (e_p_{l}, e_k_{l}, e_a_{l}, task_count, process_task_count, gram_schmidt)
 
 The modules below only OWN parameters (fp32 masters on the device); they have no forward of their own.  All
 compute happens in `VisionTransformer.features()`: ONE C call for the whole forward and ONE for the whole backward
@@ -249,6 +250,7 @@ class _Scratch:
         self.gram = None
         self.sd_key = None        # SD-LoRA: identity of the term set the executor was told about, and its device tables
         self.sd_tab = self.sd_ranks = self.sd_mag = self.sd_inv = None
+        self.prefix_on = False    # the executor's prefix mode (clhip_vit_set_prefix) as this module last left it
 
     def __deepcopy__(self, memo):
         return _Scratch()
@@ -291,6 +293,52 @@ class _VitSdFn(torch.autograd.Function):
         if vit._fwd_token != ctx.token:
             raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
         return (None, None, None) + tuple(vit._run_backward_sd(dfeat))
+
+
+class _CodaFn(torch.autograd.Function):
+    """query pass (no prefix) -> prompt assembly (clhip_coda_fwd) -> prefixed forward; backward = clhip_vit_backward_prefix -> clhip_coda_bwd.
+    `params` = K, A, P of every prompted layer, in layer order"""
+
+    @staticmethod
+    def forward(ctx, vit, layers, images, need, s_, f_, pool, length, *params):
+        q = vit._run_forward(images, None, 0, None)                      # norm(x)[:, 0] of the prompt-free forward (vit.py:121-123)
+        B, D, n, Lp = q.shape[0], vit.embed_dim, len(layers), length // 2
+        dev, (code, tdt) = q.device, _DT[vit.compute_dtype]
+        for t in params:
+            require_gpu(t)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.ClhipError("the CODA-Prompt pool must be contiguous fp32")
+        e = torch.empty(2, n, B, Lp, D, device=dev, dtype=tdt)
+        c = torch.empty(n, B, f_, device=dev)
+        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        K, A, P = params[0::3], params[1::3], params[2::3]
+        call("clhip_coda_fwd", n, q.data_ptr(), arr(K), arr(A), arr(P), arr(e[0].unbind(0)), arr(e[1].unbind(0)), c.data_ptr(), B, D, pool, length, f_, code,
+             _st())
+        lp, pk, pv = [0] * vit.depth, [None] * vit.depth, [None] * vit.depth
+        for i, l in enumerate(layers):
+            lp[l], pk[l], pv[l] = Lp, e[0, i], e[1, i]
+        feat = vit._run_forward(images, None, need, None, prefix=(lp, pk, pv))
+        ctx.vit, ctx.token, ctx.lp, ctx.layers, ctx.dims = vit, vit._fwd_token, lp, layers, (pool, length, s_, f_)
+        ctx.keep = (q, c, e)                                             # e: the executor reads the prefixes again in the backward
+        ctx.params = params
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        vit = ctx.vit
+        if vit._fwd_token != ctx.token:
+            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        q, c, _ = ctx.keep
+        pool, length, s_, f_ = ctx.dims
+        n, B, D = len(ctx.layers), q.shape[0], vit.embed_dim
+        dpk, dpv = vit._run_backward_prefix(dfeat, ctx.lp)
+        params = ctx.params
+        grads = [torch.zeros_like(t) for t in params]                    # rows outside [s, f) get no gradient
+        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        ws = torch.empty(_lib.lib().clhip_coda_ws_bytes(n, B, s_, f_) // 4, device=q.device)
+        call("clhip_coda_bwd", n, q.data_ptr(), arr(params[0::3]), arr(params[1::3]), arr(params[2::3]), c.data_ptr(), arr([dpk[l] for l in ctx.layers]),
+             arr([dpv[l] for l in ctx.layers]), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]), ws.data_ptr(), B, D, pool, length, s_, f_, _st())
+        return (None,) * 8 + tuple(grads)
 
 
 class VisionTransformer(nn.Module):
@@ -519,7 +567,8 @@ class VisionTransformer(nn.Module):
         s.ws_key = key
         return s.ws
 
-    def _run_forward(self, images, prompt_tokens, save, gram):
+    def _run_forward(self, images, prompt_tokens, save, gram, prefix=None):
+        """prefix: None, or (Lp [depth] ints, pk [depth], pv [depth] tensors or None) -- the layers with Lp > 0 attend over [prefix | tokens]"""
         require_gpu(images)
         images = images.float().contiguous()
         B = images.shape[0]
@@ -533,6 +582,14 @@ class VisionTransformer(nn.Module):
             n_prompt = prompt_tokens.shape[0]
         ws = self._workspace(s, B, n_prompt, int(bool(save)) | (2 if gram is not None else 0), dev)
         feat = torch.empty(B, self.embed_dim, device=dev, dtype=torch.float32)
+        if prefix is not None:
+            lp, pk, pv = prefix
+            ptr = lambda ts: (C.c_void_p * self.depth)(*[None if t is None else t.data_ptr() for t in ts])
+            call("clhip_vit_set_prefix", s.handle, (C.c_int * self.depth)(*lp), ptr(pk), ptr(pv))
+            s.prefix_on = True
+        elif s.prefix_on:                                    # the mode persists in the executor: every other forward runs without it
+            call("clhip_vit_set_prefix", s.handle, None, None, None)
+            s.prefix_on = False
         self.last_dropout_seed = None
         if self.adapter_dim and self.training and self.adapter_dropout > 0.0:
             # one 64-bit word from the device generator (the one init_seed seeds): no synchronisation, and the CPU generator is left alone
@@ -568,6 +625,31 @@ class VisionTransformer(nn.Module):
         call("clhip_vit_backward_adapter", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
              dprompt.data_ptr() if want_prompt else None, arr, aarr, _st())
         return dprompt, dl, dad
+
+    def _run_backward_prefix(self, dfeat, lp):
+        """-> (dpk, dpv): per layer a fp32 [B, Lp, D] tensor, None where Lp = 0"""
+        s = self._s
+        B, _ = self._last
+        dfeat = dfeat.float().contiguous()
+        dev = dfeat.device
+        dpk = [torch.empty(B, n, self.embed_dim, device=dev) if n else None for n in lp]          # the kernels write every element
+        dpv = [torch.empty(B, n, self.embed_dim, device=dev) if n else None for n in lp]
+        ptr = lambda ts: (C.c_void_p * self.depth)(*[None if t is None else t.data_ptr() for t in ts])
+        call("clhip_vit_backward_prefix", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, None, ptr(dpk), ptr(dpv),
+             _st())
+        return dpk, dpv
+
+    def coda_features(self, images, pool, train=False):
+        """ViTZoo.forward with a CODA-Prompt pool (vit.py:120-127): [B, D] fp32, the final-LN output at the cls token of the forward whose blocks
+        `pool.e_layers` attend over the assembled prefixes.  Differentiable w.r.t. the pool's tensors (rows of the running task's window)."""
+        if self.lora_rank or self.sd_lora or self.adapter_dim:
+            raise NotImplementedError("CODA-Prompt runs on the plain frozen backbone")
+        if train and pool.ortho_mu > 0:
+            raise NotImplementedError("mu > 0: the orthogonality penalty is not built (the reference's ortho_penalty calls .cuda(), prompt.py:222-223)")
+        params = pool.layer_tensors()
+        need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
+        s_, f_ = pool.window()
+        return _CodaFn.apply(self, tuple(pool.e_layers), images, need, s_, f_, pool.e_pool_size, pool.e_p_length, *params)
 
     # --------------------------------------------------------------------------------------- public forward
     def _gram_buffer(self, dev):
@@ -631,7 +713,7 @@ class VisionTransformer(nn.Module):
             tokens, reduce_sim = prompt(None, cls_features=cls_features)
             return self.features(x, tokens), reduce_sim
         if prompt is not None:
-            raise NotImplementedError("CODA / DualPrompt prompting is outside the hot-path scope (SURVEY.md section 8)")
+            raise NotImplementedError("prefix prompting goes through coda_features (ViTZoo.forward); DualPrompt is outside the hot-path scope")
         return self.features(x, None, get_input_matrix), None
 
     def debug_read(self, layer, which):
@@ -709,6 +791,81 @@ class L2PPrompt(nn.Module):
         return tokens, reduce_sim
 
 
+class CodaPromptPool(nn.Module):
+    """prompt.CodaPrompt (prompt.py:37-223): per prompted layer l in `e_layers` the components e_p_{l} [pool, length, D], their keys e_k_{l} and attention
+    vectors e_a_{l} [pool, key_dim].  Construction makes the reference's draws from torch's CPU generator in its order (prompt.py:47-64: uniform_ for p, k, a,
+    then gram_schmidt on p, k, a with one randn_like per column), so a seeded run starts from the reference's tensors bit for bit.  The module only owns the
+    parameters: VisionTransformer.coda_features assembles the prefixes (csrc/coda.hip) and runs the blocks."""
+
+    def __init__(self, emb_d, n_tasks, prompt_param, key_dim=768):
+        super().__init__()
+        self.task_count, self.emb_d, self.key_d, self.n_tasks = 0, emb_d, key_dim, n_tasks
+        self.e_pool_size, self.e_p_length, self.ortho_mu = int(prompt_param[0]), int(prompt_param[1]), prompt_param[2]
+        self.e_layers = [0, 1, 2, 3, 4]
+        if key_dim != emb_d:
+            raise NotImplementedError("the query is the backbone's cls feature: key_dim must equal the embedding width")
+        if self.e_p_length % 2 or self.e_p_length < 2:
+            raise NotImplementedError("prompt_length must be even: one half is the key prefix, the other the value prefix")
+        for e in self.e_layers:
+            p = nn.init.uniform_(torch.empty(self.e_pool_size, self.e_p_length, emb_d, dtype=torch.float32))
+            k = nn.init.uniform_(torch.empty(self.e_pool_size, self.key_d, dtype=torch.float32))
+            a = nn.init.uniform_(torch.empty(self.e_pool_size, self.key_d, dtype=torch.float32))
+            setattr(self, f"e_p_{e}", self.gram_schmidt(p))
+            setattr(self, f"e_k_{e}", self.gram_schmidt(k))
+            setattr(self, f"e_a_{e}", self.gram_schmidt(a))
+
+    def window(self):
+        """(s, f): the components [0, f) are used, [s, f) train (prompt.py:169-186)"""
+        pt = int(self.e_pool_size / self.n_tasks)
+        return int(self.task_count * pt), int((self.task_count + 1) * pt)
+
+    def layer_tensors(self):
+        """K, A, P of every prompted layer, in layer order"""
+        return [getattr(self, f"e_{w}_{e}") for e in self.e_layers for w in ("k", "a", "p")]
+
+    @torch.no_grad()
+    def process_task_count(self):
+        """prompt.py:76-96: move the window on and re-draw its components.  Nothing in the reference calls it (see model/codaprompt.py)"""
+        self.task_count += 1
+        for e in self.e_layers:
+            for w in ("k", "a", "p"):                                  # (the reference's order: k, a, p)
+                old = getattr(self, f"e_{w}_{e}")
+                setattr(self, f"e_{w}_{e}", nn.Parameter(self.gram_schmidt(old.detach().cpu()).to(old.device)))
+
+    @torch.no_grad()
+    def gram_schmidt(self, vv):
+        """prompt.py:100-156: columns [s, f) of the (flattened, transposed) tensor become fresh Gaussian draws, each orthogonalised against ALL columns
+        before it -- the columns beyond the window among them, which are still zero -- and normalised; columns below s are kept, columns at or beyond f are
+        zero.  Same operations in the same order as the reference, so fp32 results agree bit for bit."""
+        shape = vv.shape
+        vv = vv.reshape(shape[0], -1).T
+        uu = torch.zeros_like(vv)
+        s, f = self.window()
+        if s > 0:
+            uu[:, :s] = vv[:, :s].clone()
+        for k in range(s, f):
+            redo = True
+            while redo:
+                redo = False
+                vk = torch.randn_like(vv[:, k])
+                uk = 0
+                for j in range(k):
+                    if redo:
+                        continue
+                    uj = uu[:, j].clone()
+                    den = (uj * uj).sum()
+                    if den < 1e-8:
+                        redo = True                                      # a degenerate earlier column: draw again
+                    else:
+                        uk = uk + (vk * uj).sum() / den * uj
+                if not redo:
+                    uu[:, k] = vk - uk
+        for k in range(s, f):
+            uk = uu[:, k].clone()
+            uu[:, k] = uk / uk.norm()
+        return nn.Parameter(uu.T.reshape(shape).contiguous())
+
+
 class ViTZoo(nn.Module):
     """core/model/backbone/vit.py:43-139.  Extra kwargs (img_size, patch_size, embed_dim, depth, num_heads, dtype) size
     the model for tests; the defaults are the reference's hard-coded ViT-B/16."""
@@ -749,16 +906,24 @@ class ViTZoo(nn.Module):
         self.feat.load_state_dict({k: v for k, v in out.items() if k in own and tuple(v.shape) == tuple(own[k].shape)}, strict=False)
 
     def create_prompt(self, prompt_flag, **kwargs):
+        if prompt_flag == "l2p":
+            self.prompt = L2PPrompt(**kwargs)
+        elif prompt_flag == "coda":
+            kwargs.setdefault("key_dim", self.feat_dim)                    # (vit.py:97 hard-codes 768 for both; here the backbone's width)
+            self.prompt = CodaPromptPool(self.feat_dim, **kwargs)
+        else:
+            raise NotImplementedError("only the L2P and CODA-Prompt pools are on the hot path (SURVEY.md section 8)")
         self.prompt_flag = prompt_flag
-        if prompt_flag != "l2p":
-            raise NotImplementedError("only the L2P prompt pool is on the hot path (SURVEY.md section 8)")
-        self.prompt = L2PPrompt(**kwargs)
 
     def forward(self, image, text=None, pen=False, train=False, **kwargs):
         if self.prompt_flag == "l2p":
             with torch.no_grad():
                 cls_features = self.feat(image, prompt_flag="l2p")
             return self.feat(image, prompt=self.prompt, cls_features=cls_features, prompt_flag="l2p")
+        if self.prompt_flag == "coda":
+            # vit.py:120-138: query pass without gradient, prompted pass, the cls feature; the prompt loss is the orthogonality penalty, 0 at mu = 0
+            out = self.feat.coda_features(image, self.prompt, train=train)
+            return (out, torch.zeros(1, device=out.device)) if train else out
         if self.prompt is not None:
             raise NotImplementedError
         out, _ = self.feat(image, **kwargs)

@@ -1,0 +1,165 @@
+"""csrc/attn_prefix.hip through the C ABI on the MI355X, against the references and bounds tests/test_vit_ops_kernels_gpu.py holds csrc/attn.hip to.
+
+No reference or bound of its own: prefix attention over (N, Lp) IS plain attention over Lp + N tokens whose first Lp rows have keys and values, an
+arbitrary query and zero dout (their dS is exactly zero, they contribute nothing to dK / dV; tests/test_coda_cpu.py checks the identity in fp64).  Every
+case builds that packed input, calls vit_refs.attn_ref / attn_logit_abs / attn_cancel_bound on it and holds the kernels to the bounds of
+`run_attention` there, with its u, v rule (eps_o = 2^-9 in the bf16 modes, eps_ds = 2^-9 where dS is packed to bf16 for the MFMA, T 2^-24 otherwise).
+Each tensor is judged per (batch, head) on the rows the kernel produces, relative to the max|ref| of THOSE rows (never looser than the packed block's).
+dpk / dpv are fp32: their bound is the dk / dv bound without the final bf16 store step (half a bf16 ulp, 2^-9, off the relative part)."""
+import pytest
+import torch
+
+import vit_refs as V
+from vit_refs import U, larger
+from test_vit_ops_kernels_gpu import CODE, DEV, GUARD, blocked, check, dev, guard_ok, measure, nan_out, p, st
+
+pytestmark = pytest.mark.gpu
+
+from libcontinual_amd import _lib           # noqa: E402
+from libcontinual_amd._lib import call      # noqa: E402
+
+
+def split(big, bd, B, N, Lp, D):
+    """packed [B * (Lp + N), 3D] / [B * (Lp + N), D] -> qkv [B * N, 3D], pk, pv [B * Lp, D], dout [B * N, D] (the prefix rows' dout is zero)"""
+    T = Lp + N
+    x = big.reshape(B, T, 3, D)
+    assert float(bd.reshape(B, T, D)[:, :Lp].abs().max()) == 0.0
+    return (x[:, Lp:].reshape(B * N, 3 * D).contiguous(), x[:, :Lp, 1].reshape(B * Lp, D).contiguous(), x[:, :Lp, 2].reshape(B * Lp, D).contiguous(),
+            bd.reshape(B, T, D)[:, Lp:].reshape(B * N, D).contiguous())
+
+
+def packed_inputs(B, N, Lp, H, hd, seed, dt):
+    big, bd = V.attn_inputs(B, N + Lp, H, hd, seed, dt)
+    bd = bd.reshape(B, N + Lp, H * hd).clone()
+    bd[:, :Lp] = 0
+    return big, bd.reshape(B * (N + Lp), H * hd)
+
+
+def launch(qkv, pk, pv, dout, B, N, Lp, H, hd, dt):
+    D = H * hd
+    q_, k_, v_, do_ = dev(qkv, dt), dev(pk, dt), dev(pv, dt), dev(dout, dt)
+    out, out2 = nan_out(B * N, D, dt), nan_out(B * N, D, dt)
+    lse = torch.full((B * H * N + 8,), float("nan"), device=DEV)
+    lse[B * H * N:] = GUARD
+    dqkv = nan_out(B * N, 3 * D, dt)
+    dpk, dpv = nan_out(B * Lp, D, "f32"), nan_out(B * Lp, D, "f32")
+    dsum = torch.empty(B * H * N, device=DEV)
+    call("clhip_attn_prefix_fwd", p(q_), p(k_), p(v_), p(out), p(lse), B, N, Lp, H, D, CODE[dt], st())
+    call("clhip_attn_prefix_fwd", p(q_), p(k_), p(v_), p(out2), None, B, N, Lp, H, D, CODE[dt], st())
+    call("clhip_attn_prefix_bwd", p(q_), p(k_), p(v_), p(out), p(lse), p(do_), p(dqkv), p(dpk), p(dpv), p(dsum), B, N, Lp, H, D, CODE[dt], st())
+    torch.cuda.synchronize()
+    return (q_, k_, v_, do_), out, out2, lse, dqkv, dpk, dpv, dsum
+
+
+def run_prefix(big, bd, B, N, Lp, H, hd, dt, tag):
+    """forward (with and without lse), backward, zero-dout backward; every output against the fp64 reference of the packed form per (batch, head)"""
+    D, T = H * hd, N + Lp
+    qkv, pk, pv, dout = split(big, bd, B, N, Lp, D)
+    ins, out, out2, lse, dqkv, dpk, dpv, dsum = launch(qkv, pk, pv, dout, B, N, Lp, H, hd, dt)
+    assert guard_ok(out, B * N) and guard_ok(out2, B * N) and guard_ok(dqkv, B * N) and bool((lse[B * H * N:] == GUARD).all())
+    assert guard_ok(dpk, B * Lp) and guard_ok(dpv, B * Lp)
+    bits = torch.int16 if dt == "bf16" else torch.int32
+    assert torch.equal(out[:B * N].view(bits), out2[:B * N].view(bits))
+    for t in (out[:B * N], lse[:B * H * N], dqkv[:B * N], dpk[:B * Lp], dpv[:B * Lp]):
+        assert bool(torch.isfinite(t.float()).all()), tag
+    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = V.attn_ref(big, bd, B, T, H, hd)
+    assert float(ref_dq[:, :, :Lp].abs().max()) == 0.0                       # zero dout: the prefix rows' queries get nothing, as the kernel assumes
+    labs = V.attn_logit_abs(big, B, T, H, hd)[:, :, Lp:]                     # [B,H,N]: the token queries
+    cond = hd * U * labs
+    bf = dt == "bf16"
+    mfma = bf and hd == 64
+    cq, ck = V.attn_cancel_bound(big, bd, B, T, H, hd, 2.0 ** -9 if bf else U, 2.0 ** -9 if mfma else T * U)
+    g_o = V.heads(V.f64(out[:B * N]), B, N, H, hd)
+    gq, gk, gv = V.split_qkv(V.f64(dqkv[:B * N]), B, N, H, hd)
+    gpk, gpv = V.heads(V.f64(dpk[:B * Lp]), B, Lp, H, hd), V.heads(V.f64(dpv[:B * Lp]), B, Lp, H, hd)
+
+    def amax(t):
+        return t.abs().amax(dim=(-1, -2), keepdim=True)
+    tok, pre = (lambda t: t[:, :, Lp:]), (lambda t: t[:, :, :Lp])
+    cmax = cond.amax(-1)[..., None, None]
+    store = 2.0 ** -9 if bf else 0.0                                          # the bf16 store step dpk / dpv do not have
+    blocked(f"{tag} out", g_o, tok(ref_o), V.ATTN_OUT[dt], cond[..., None] * amax(tok(ref_o)).expand_as(tok(ref_o)))
+    blocked(f"{tag} dq", gq, tok(ref_dq), V.ATTN_GRAD[dt], tok(cq) + cond[..., None] * amax(tok(ref_dq)))
+    blocked(f"{tag} dk", gk, tok(ref_dk), V.ATTN_GRAD[dt], tok(ck) + cmax * amax(tok(ref_dk)))
+    blocked(f"{tag} dv", gv, tok(ref_dv), V.ATTN_GRAD[dt], (cmax * amax(tok(ref_dv))).expand_as(tok(ref_dv)))
+    blocked(f"{tag} dpk", gpk, pre(ref_dk), V.ATTN_GRAD[dt] - store, pre(ck) + cmax * amax(pre(ref_dk)))
+    blocked(f"{tag} dpv", gpv, pre(ref_dv), V.ATTN_GRAD[dt] - store, (cmax * amax(pre(ref_dv))).expand_as(pre(ref_dv)))
+    g_lse = V.f64(lse[:B * H * N]).reshape(B, H, N)
+    measure(f"{tag} lse abs", g_lse, tok(ref_lse))
+    check(f"{tag} lse", g_lse, tok(ref_lse), larger(torch.full_like(tok(ref_lse), V.measured(V.LSE_ABS)), V.lse_floor(cond, T, tok(ref_lse))))
+    zero = torch.zeros_like(ins[3])
+    dz, zk, zv = nan_out(B * N, 3 * D, dt), nan_out(B * Lp, D, "f32"), nan_out(B * Lp, D, "f32")
+    call("clhip_attn_prefix_bwd", p(ins[0]), p(ins[1]), p(ins[2]), p(out), p(lse), p(zero), p(dz), p(zk), p(zv), p(dsum), B, N, Lp, H, D, CODE[dt], st())
+    torch.cuda.synchronize()
+    assert bool((dz[:B * N].float() == 0).all()) and guard_ok(dz, B * N), tag
+    assert bool((zk[:B * Lp] == 0).all()) and bool((zv[:B * Lp] == 0).all()) and guard_ok(zk, B * Lp) and guard_ok(zv, B * Lp), tag
+
+
+MFMA_CASES = [(1, 1), (12, 4), (13, 4), (16, 1), (16, 16), (197, 4), (197, 10), (197, 11), (197, 12), (222, 4), (252, 4), (255, 1)]
+
+
+@pytest.mark.parametrize("N,Lp", MFMA_CASES)
+def test_prefix_attention_mfma(N, Lp):
+    """bf16, head dim 64, H = 3, B = 2: one key tile (12,4); the prefix pushes into a second (13,4); two key tiles over one query tile (16,1), (16,16); CODA's
+    201 keys (197,4); 208 keys = 13 full tiles (197,11); 14 key tiles over 13 query tiles (197,12); 256 keys (252,4), (255,1): forward <0>, backward generic"""
+    big, bd = packed_inputs(2, N, Lp, 3, 64, 700 + 3 * N + Lp, "bf16")
+    run_prefix(big, bd, 2, N, Lp, 3, 64, "bf16", f"prefix bf16 hd64 N={N} Lp={Lp}")
+
+
+@pytest.mark.parametrize("dt,hd", [("f32", 64), ("f32", 32), ("bf16", 32)])
+@pytest.mark.parametrize("N,Lp", [(1, 1), (17, 4), (50, 5), (197, 4)])
+def test_prefix_attention_generic(dt, hd, N, Lp):
+    big, bd = packed_inputs(2, N, Lp, 3, hd, 900 + 3 * N + Lp, dt)
+    run_prefix(big, bd, 2, N, Lp, 3, hd, dt, f"prefix {dt} hd{hd} N={N} Lp={Lp}")
+
+
+def test_prefix_attention_more_workgroups_than_cus():
+    """B * H = 264 workgroups at (17, 4)"""
+    big, bd = packed_inputs(22, 17, 4, 12, 64, 417, "bf16")
+    run_prefix(big, bd, 22, 17, 4, 12, 64, "bf16", "prefix bf16 hd64 BH=264")
+
+
+@pytest.mark.parametrize("dt,hd", [("bf16", 64), ("f32", 64)])
+@pytest.mark.parametrize("N,Lp", [(193, 4), (197, 4), (204, 4)])
+def test_prefix_attention_shifted_logits(dt, hd, N, Lp):
+    """vit_refs.attn_shifted_inputs(2, N + Lp, 3, hd, seed): a query row with every logit near -128 (lse < -100: P of a padded key overflows in the
+    backward's phase A unless it is masked), one near +128, a one-hot row, a head of identical keys.  The generator puts its special QUERY rows at 0, 1, 2;
+    a prefix row's query is never used, so the LAST Lp generated rows serve as the prefix (moved to the front of the packed form) and rows 0.. stay
+    tokens: the softmax does not depend on the order of the keys."""
+    T, D = N + Lp, 3 * hd
+    x, d = V.attn_shifted_inputs(2, T, 3, hd, 500 + T)
+    x, d = x.reshape(2, T, 3 * D), d.reshape(2, T, D).clone()
+    d[:, N:] = 0
+    big = torch.cat((x[:, N:], x[:, :N]), dim=1).reshape(2 * T, 3 * D)
+    bd = torch.cat((d[:, N:], d[:, :N]), dim=1).reshape(2 * T, D)
+    assert float(V.attn_ref(big, bd, 2, T, 3, hd)[1][0, 0, Lp + V.SHIFT_LOW]) < -88.7
+    run_prefix(big, bd, 2, N, Lp, 3, hd, dt, f"prefix shifted {dt} hd{hd} N={N} Lp={Lp}")
+
+
+@pytest.mark.parametrize("dt,hd,N,Lp", [("bf16", 64, 197, 4), ("bf16", 64, 252, 4), ("f32", 64, 50, 5)])
+def test_prefix_attention_is_bit_reproducible(dt, hd, N, Lp):
+    big, bd = packed_inputs(2, N, Lp, 3, hd, 31, dt)
+    qkv, pk, pv, dout = split(big, bd, 2, N, Lp, 3 * hd)
+    a = launch(qkv, pk, pv, dout, 2, N, Lp, 3, hd, dt)
+    b = launch(qkv, pk, pv, dout, 2, N, Lp, 3, hd, dt)
+    for x, y in zip(a[1:7], b[1:7]):
+        assert torch.equal(x.view(torch.uint8), y.view(torch.uint8))
+
+
+def test_prefix_attention_rejects_bad_arguments():
+    """Lp = 0, N + Lp = 257, head dim 128, D % H != 0: the error code, and the NaN-filled outputs untouched"""
+    for B, N, Lp, H, D in [(1, 16, 0, 1, 64), (1, 253, 4, 1, 64), (1, 16, 4, 1, 128), (1, 16, 4, 3, 64)]:
+        qkv = torch.zeros(B * N, 3 * D, device=DEV, dtype=torch.bfloat16)
+        pk = torch.zeros(B * max(Lp, 1), D, device=DEV, dtype=torch.bfloat16)
+        out, dqkv = nan_out(B * N, D, "bf16"), nan_out(B * N, 3 * D, "bf16")
+        dpk, dpv = nan_out(B * max(Lp, 1), D, "f32"), nan_out(B * max(Lp, 1), D, "f32")
+        lse = torch.full((B * H * N,), float("nan"), device=DEV)
+        dsum = torch.empty(B * H * N, device=DEV)
+        dout = torch.zeros(B * N, D, device=DEV, dtype=torch.bfloat16)
+        with pytest.raises(_lib.ClhipError):
+            call("clhip_attn_prefix_fwd", p(qkv), p(pk), p(pk), p(out), p(lse), B, N, Lp, H, D, CODE["bf16"], st())
+        with pytest.raises(_lib.ClhipError):
+            call("clhip_attn_prefix_bwd", p(qkv), p(pk), p(pk), p(out), p(lse), p(dout), p(dqkv), p(dpk), p(dpv), p(dsum), B, N, Lp, H, D, CODE["bf16"], st())
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out[:B * N].float()).all()) and bool(torch.isnan(dqkv[:B * N].float()).all()) and bool(torch.isnan(lse).all())
+        assert bool(torch.isnan(dpk[:-1]).all()) and bool(torch.isnan(dpv[:-1]).all())
