@@ -598,7 +598,8 @@ int clhip_attn_bwd(const void* qkv, const void* out, const float* lse, const voi
 /* Prefix-tuning attention: MultiHeadAttention.forward with `prompt` given (transformer.py:175-180: k = cat(pk, k), v = cat(pv, v) per sample and head).
  * qkv, out, lse, dout, dqkv exactly as in clhip_attn_fwd / _bwd; pk, pv [B, Lp, D] in the compute dtype (column = head*d + i): per-sample key and value
  * rows that have no query.  Per (batch, head) the N token queries attend over the Lp + N keys [prefix | tokens].  dpk, dpv [B, Lp, D] fp32 are WRITTEN
- * (not accumulated); deterministic, no atomics.  1 <= Lp, N + Lp <= 256, d <= 64; anything else is CLHIP_EINVAL.  csrc/attn_prefix.hip. */
+ * (not accumulated); deterministic, no atomics.  1 <= Lp, N + Lp <= 256, d <= 64; anything else is CLHIP_EINVAL.  csrc/attn.hip (the prefix
+ * instantiation of the kernels behind clhip_attn_fwd / _bwd). */
 int clhip_attn_prefix_fwd(const void* qkv, const void* pk, const void* pv, void* out, float* lse, int B, int N, int Lp, int H, int D, int dtype, void* stream);
 int clhip_attn_prefix_bwd(const void* qkv, const void* pk, const void* pv, const void* out, const float* lse, const void* dout, void* dqkv, float* dpk,
                           float* dpv, float* dsum_ws, int B, int N, int Lp, int H, int D, int dtype, void* stream);

@@ -1,11 +1,21 @@
 // attn.hip -- multi-head self-attention of the ViT path, forward and backward, directly on the packed qkv
-// activation (reference core/model/backbone/transformer.py:169-197 and :239-274).
+// activation (reference core/model/backbone/transformer.py:169-197 and :239-274), in the plain form and in the
+// prefix-tuning form (`prompt` given, :175-180).
 //
 // The reference reshapes qkv to [3,B,H,N,d], materialises the [B,H,N,N] score matrix, softmaxes it in a separate
 // pass, multiplies by V and transposes back.  Here one workgroup owns one (batch, head): K and V (and for the
 // backward also Q and dO) of that head are staged ONCE in LDS straight from the [B*N, 3D] qkv buffer (row stride
 // 3D, head offset h*64 -- no permute), the score tile never leaves registers, and the output is written in the
 // [B*N, D] layout the projection GEMM consumes.  N <= 256 (197 / 222 tokens on this path), head dim 64.
+//
+// Prefix form (PFX): every sample brings Lp extra key and value rows (pk, pv: [B, Lp, D], column = head*d + i) that have
+// NO query.  The N token queries attend over the Lp + N keys [prefix | tokens]; the reference concatenates k and v
+// ([B,H,Lp+N,d]) and runs the plain product.  Here the prefix never becomes tokens: K and V are staged from TWO sources
+// (LDS row r of K / V is key r: r < Lp the prefix, r - Lp the token), and the key-tile count ceil((N + Lp) / 16) is not
+// the query-tile count ceil(N / 16).  The backward returns dqkv for the tokens and dpk, dpv [B, Lp, D] in fp32 (written,
+// not accumulated; no atomics: each key row has one owner).  Plain attention is the prefix form with Lp = 0: every kernel
+// that has both forms is ONE template on the flag PFX, whose plain instantiation sees Lp as the literal 0 and never touches
+// the prefix fields (the plain ViT steps' kernels keep their instruction streams; profiles/attn_unify.md).
 //
 // MFMA formulation (wave64, v_mfma_f32_16x16x32_bf16; D layout col = lane&15, rows = (lane>>4)*4+e):
 //   fwd  S^T[key,q] = K . Q^T         (A = K rows, B = Q rows: both 16-byte LDS / global reads)
@@ -15,7 +25,8 @@
 //   bwd  phase A (wave <- query tiles): dQ^T[d,q]  = K^T . dS^T
 //        phase B (wave <- key tiles):   dV^T[d,k]  = dO^T . P,   dK^T[d,k] = Q^T . dS
 //        with P = exp(S*scale - lse), dS = P * (dP - rowsum(dO*O)), dP = dO . V^T; lse is saved by the forward.
-// fp32 (parity mode) and odd head sizes use the generic one-wave-per-row kernels at the end of the file.
+// fp32 (parity mode), odd head sizes and a backward whose four tiles do not fit the LDS use the generic one-wave-per-row
+// kernels at the end of the file.
 #include "common.h"
 
 namespace {
@@ -25,6 +36,7 @@ struct AttnParams {
     const void* dout; void* dqkv; float* dsum;     // backward only (dsum: [B,H,N] scratch, generic path)
     int B, N, H, D;
     float scale;
+    const void* pk; const void* pv; float* dpk; float* dpv; int Lp;     // prefix form only, behind the plain fields: their kernarg offsets are the plain kernels'
 };
 
 constexpr int KP = 160;      // LDS pitch (bytes) of a 64-element bf16 row: ds_read_b128 and tr reads are conflict-free
@@ -37,40 +49,62 @@ __device__ __forceinline__ uint4 pack8(const f32x4& a, const f32x4& b) {
 }
 __device__ __forceinline__ uint4 ldsq(const char* base, int off) { return *reinterpret_cast<const uint4*>(base + off); }
 
-// stage rows [0, NP2) of one head's 64-wide slice (global row stride `ld` elements) into LDS, zero beyond N
-__device__ __forceinline__ void stage_rows(char* dst, const bf16_t* src, size_t ld, int N, int NP2) {
-    for (int idx = threadIdx.x; idx < NP2 * 8; idx += blockDim.x) {
+// 16-byte chunk c of key (or value) row `row` of one 64-wide head: the prefix (row pitch D) below Lp, the token row - Lp (row pitch ld) below Lt = Lp + N, zero beyond
+template <bool PFX>
+__device__ __forceinline__ uint4 key_chunk(const bf16_t* pre, size_t D, const bf16_t* tok, size_t ld, int Lp, int Lt, int row, int c) {
+    if (PFX && row < Lp) return *reinterpret_cast<const uint4*>(pre + (size_t)row * D + c * 8);
+    if (row < Lt) return *reinterpret_cast<const uint4*>(tok + (size_t)(row - Lp) * ld + c * 8);
+    return make_uint4(0, 0, 0, 0);
+}
+
+// the plain form's staging loop: key (or value) rows [0, rows) of one head into LDS
+__device__ __forceinline__ void stage_rows(char* dst, const bf16_t* tok, size_t ld, int Lt, int rows) {
+    for (int idx = threadIdx.x; idx < rows * 8; idx += blockDim.x) {
         const int row = idx >> 3, c = idx & 7;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (row < N) v = *reinterpret_cast<const uint4*>(src + (size_t)row * ld + c * 8);
-        *reinterpret_cast<uint4*>(dst + row * KP + c * 16) = v;
+        *reinterpret_cast<uint4*>(dst + row * KP + c * 16) = key_chunk<false>(nullptr, 0, tok, ld, 0, Lt, row, c);
     }
 }
 
-// NKT = number of 16-key tiles (compile time: 13 / 14 for N = 197 / 222; 0 = run-time count, up to 16).  Instruction diet
+// one head's rows of a prefix matrix (pk or pv); the plain form has none and never reads the field
+template <bool PFX>
+__device__ __forceinline__ const bf16_t* prefix_head(const void* pre, int b, int Lp, int D, int h) {
+    return PFX ? static_cast<const bf16_t*>(pre) + (size_t)b * Lp * D + h * 64 : nullptr;
+}
+
+// NKT = number of 16-key tiles (compile time: 13 / 14 for 197..208 / 209..224 keys; 0 = run-time count, up to 16).  Instruction diet
 // (PMC of the first version: 18 VALU per MFMA, the kernel was issue-bound): the softmax scale is folded into the exponent
 // (one v_fma + one v_exp per score, exp2 domain), only the last key tile is masked, P stays unnormalised in bf16 and 1/sum
 // is applied to the 16 output accumulators instead of the 52 probabilities.
-template <int NKT>
+template <int NKT, bool PFX>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
     const int bh = blockIdx.x, b = bh / p.H, h = bh - b * p.H;
-    const int N = p.N, D = p.D;
-    const int nKT = NKT > 0 ? NKT : (N + 15) >> 4;
+    const int N = p.N, D = p.D, Lp = PFX ? p.Lp : 0, Lt = N + Lp;
+    const int nKT = NKT > 0 ? NKT : (Lt + 15) >> 4, nQT = PFX ? (N + 15) >> 4 : nKT;     // plain: the two counts are one
     constexpr int KTMAX = NKT > 0 ? NKT : 16;
-    const int NP2 = ((nKT + 1) & ~1) * 16;
+    const int NK2 = ((nKT + 1) & ~1) * 16;
     const size_t ld = 3 * (size_t)D;
     const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (size_t)b * N * ld + h * 64;
     char* Ks = smem;
-    char* Vs = smem + NP2 * KP;
-    stage_rows(Ks, base + D, ld, N, NP2);
-    stage_rows(Vs, base + 2 * D, ld, N, NP2);
+    char* Vs = smem + NK2 * KP;
+    if constexpr (PFX) {         // K and V in one loop: half the dependent round trips (50.6 -> 50.1 us at (197, 4), B x H = 128 x 12; profiles/attn_unify.md)
+        const bf16_t* pkb = prefix_head<PFX>(p.pk, b, Lp, D, h);
+        const bf16_t* pvb = prefix_head<PFX>(p.pv, b, Lp, D, h);
+        for (int idx = tid; idx < NK2 * 8; idx += 256) {
+            const int row = idx >> 3, cc = idx & 7;
+            *reinterpret_cast<uint4*>(Ks + row * KP + cc * 16) = key_chunk<PFX>(pkb, D, base + D, ld, Lp, Lt, row, cc);
+            *reinterpret_cast<uint4*>(Vs + row * KP + cc * 16) = key_chunk<PFX>(pvb, D, base + 2 * D, ld, Lp, Lt, row, cc);
+        }
+    } else {                     // a loop each: the instruction stream of the plain ViT steps' forward stays what it was
+        stage_rows(Ks, base + D, ld, Lt, NK2);
+        stage_rows(Vs, base + 2 * D, ld, Lt, NK2);
+    }
     __syncthreads();
     const float c = p.scale * 1.4426950408889634f;          // scores -> exp2 domain
     const int last0 = (nKT - 1) * 16 + g * 4;               // first key this lane holds in the last tile
 
-    for (int qt = wave; qt < nKT; qt += 4) {
+    for (int qt = wave; qt < nQT; qt += 4) {
         const int qrow = qt * 16 + l15;
         const bool qok = qrow < N;
         uint4 qf[2];
@@ -87,7 +121,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
                 for (int kk = 0; kk < 2; ++kk) s[kt] = mfma_bf16(ldsq(Ks, (kt * 16 + l15) * KP + (g + 4 * kk) * 16), qf[kk], s[kt]);
                 if (kt == nKT - 1) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) if (last0 + e >= N) s[kt][e] = -INFINITY;
+                    for (int e = 0; e < 4; ++e) if (last0 + e >= Lt) s[kt][e] = -INFINITY;
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) mx = fmaxf(mx, s[kt][e]);
@@ -134,47 +168,88 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
 
 constexpr int BWD_WAVES = 16;     // LDS (Q, K, V, dO of one head) limits the CU to one workgroup: give it 16 waves (4 per SIMD; 8 waves: 166 us, 16: 141 us)
 
+// The general backward: any tile count.  LDS: Q and dO have NQ2 rows (query tiles rounded to a pair), K and V have NK2 rows (key tiles rounded to a pair).
+// Every global read of the prologue is issued before the first LDS write (ONE round trip; with one workgroup per CU nothing would overlap more): the four
+// tiles' chunks and, for the thread that owns a query row, its lse and O row.  Phase A (wave <- query tile) walks the key-tile pairs, phase B (wave <- key tile)
+// the query-tile pairs; phase B owns the prefix key rows too and stores their dK / dV columns to dpk / dpv in fp32.
+// Masks: a padded QUERY has lse = +inf, so P = 0.  A padded KEY meets a real query row in phase A, where P = exp2(0 - lse log2 e) overflows for lse < -88.7
+// and dS = inf * x is not finite (see tileA below): the last key tile and the padding tile behind it set P = 0 by key index.  In phase B a padded key column
+// is computed as zero (kok) and never stored.
+template <bool PFX>
 __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
     const int bh = blockIdx.x, b = bh / p.H, h = bh - b * p.H;
-    const int N = p.N, D = p.D, nKT = (N + 15) >> 4, NP2 = ((nKT + 1) & ~1) * 16, nPair = NP2 >> 5;
+    const int N = p.N, D = p.D, Lp = PFX ? p.Lp : 0, Lt = N + Lp;
+    const int nQT = (N + 15) >> 4, nKT = (Lt + 15) >> 4;
+    const int NQ2 = ((nQT + 1) & ~1) * 16, NK2 = ((nKT + 1) & ~1) * 16, nQPair = NQ2 >> 5, nKPair = NK2 >> 5;
     const size_t ld = 3 * (size_t)D;
     const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (size_t)b * N * ld + h * 64;
+    const bf16_t* pkb = prefix_head<PFX>(p.pk, b, Lp, D, h);
+    const bf16_t* pvb = prefix_head<PFX>(p.pv, b, Lp, D, h);
     const bf16_t* dob = static_cast<const bf16_t*>(p.dout) + (size_t)b * N * D + h * 64;
     const bf16_t* ob = static_cast<const bf16_t*>(p.out) + (size_t)b * N * D + h * 64;
     bf16_t* dqb = static_cast<bf16_t*>(p.dqkv) + (size_t)b * N * ld + h * 64;
     char* Qs = smem;
-    char* Ks = Qs + NP2 * KP;
-    char* Vs = Ks + NP2 * KP;
-    char* Gs = Vs + NP2 * KP;                                  // dO
-    float* lse_s = reinterpret_cast<float*>(Gs + NP2 * KP);    // [NP2]  lse * log2(e)  (+inf beyond N -> P = 0)
-    float* dq_s = lse_s + NP2;                                 // [NP2]  rowsum(dO * O)
-    stage_rows(Qs, base, ld, N, NP2);
-    stage_rows(Ks, base + D, ld, N, NP2);
-    stage_rows(Vs, base + 2 * D, ld, N, NP2);
-    stage_rows(Gs, dob, D, N, NP2);
-    for (int q = tid; q < NP2; q += 64 * BWD_WAVES) {
-        float dsum = 0.f, l = INFINITY;
-        if (q < N) {
-            l = p.lse[((size_t)b * p.H + h) * N + q];
+    char* Gs = Qs + NQ2 * KP;                                  // dO
+    char* Ks = Gs + NQ2 * KP;
+    char* Vs = Ks + NK2 * KP;
+    float* lse_s = reinterpret_cast<float*>(Vs + NK2 * KP);    // [NQ2]  lse * log2(e)  (+inf beyond N -> P = 0)
+    float* dq_s = lse_s + NQ2;                                 // [NQ2]  rowsum(dO * O)
+    constexpr int CH = (256 * 8) / (64 * BWD_WAVES);           // chunks per thread of the largest tile (256 rows)
+    uint4 sq[CH], sg[CH], sk[CH], sv[CH], orow[8];
+    float lraw = INFINITY;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                float x[8], y[8];
-                load8<bf16_t>(dob + (size_t)q * D + c * 8, x);
-                load8<bf16_t>(ob + (size_t)q * D + c * 8, y);
+    for (int i = 0; i < CH; ++i) {
+        const int idx = tid + i * 64 * BWD_WAVES, row = idx >> 3, cc = idx & 7;
+        sq[i] = sg[i] = make_uint4(0, 0, 0, 0);
+        if (row < N) {
+            sq[i] = *reinterpret_cast<const uint4*>(base + (size_t)row * ld + cc * 8);
+            sg[i] = *reinterpret_cast<const uint4*>(dob + (size_t)row * D + cc * 8);
+        }
+        sk[i] = key_chunk<PFX>(pkb, D, base + D, ld, Lp, Lt, row, cc);
+        sv[i] = key_chunk<PFX>(pvb, D, base + 2 * D, ld, Lp, Lt, row, cc);
+    }
+    if (tid < N) {
+        lraw = p.lse[((size_t)b * p.H + h) * N + tid];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) dsum += x[j] * y[j];
+        for (int cc = 0; cc < 8; ++cc) orow[cc] = *reinterpret_cast<const uint4*>(ob + (size_t)tid * D + cc * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int idx = tid + i * 64 * BWD_WAVES, row = idx >> 3, cc = idx & 7;
+        if (row < NQ2) {
+            *reinterpret_cast<uint4*>(Qs + row * KP + cc * 16) = sq[i];
+            *reinterpret_cast<uint4*>(Gs + row * KP + cc * 16) = sg[i];
+        }
+        if (row < NK2) {
+            *reinterpret_cast<uint4*>(Ks + row * KP + cc * 16) = sk[i];
+            *reinterpret_cast<uint4*>(Vs + row * KP + cc * 16) = sv[i];
+        }
+    }
+    __syncthreads();
+    if (tid < NQ2) {
+        float dsum = 0.f;
+        if (tid < N) {
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) {
+                const uint4 xg = ldsq(Gs, tid * KP + cc * 16);
+                const unsigned xw[4] = {xg.x, xg.y, xg.z, xg.w}, yw[4] = {orow[cc].x, orow[cc].y, orow[cc].z, orow[cc].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    dsum += __uint_as_float(xw[j] << 16) * __uint_as_float(yw[j] << 16);
+                    dsum += __uint_as_float(xw[j] & 0xffff0000u) * __uint_as_float(yw[j] & 0xffff0000u);
+                }
             }
         }
-        lse_s[q] = l * 1.4426950408889634f;
-        dq_s[q] = dsum;
+        lse_s[tid] = lraw * 1.4426950408889634f;
+        dq_s[tid] = dsum;
     }
     __syncthreads();
     const float c = p.scale * 1.4426950408889634f;          // scores -> exp2 domain
 
     // ---- phase A: dQ.  wave <- query tile; per key-tile pair: S^T, dP^T (D layout: rows key g*4+e, col q l15)
-    for (int qt = wave; qt < nKT; qt += BWD_WAVES) {
+    for (int qt = wave; qt < nQT; qt += BWD_WAVES) {
         const int qrow = qt * 16 + l15;
         uint4 qf[2], gf[2];
 #pragma unroll
@@ -186,7 +261,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
         f32x4 acc[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) acc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int ks = 0; ks < nPair; ++ks) {
+        for (int ks = 0; ks < nKPair; ++ks) {
             f32x4 ds[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -197,11 +272,11 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
                     s = mfma_bf16(ldsq(Ks, krow * KP + (g + 4 * kk) * 16), qf[kk], s);
                     dp = mfma_bf16(ldsq(Vs, krow * KP + (g + 4 * kk) * 16), gf[kk], dp);
                 }
-                const bool tail = (2 * ks + t) >= nKT - 1;               // only the last key tile holds keys >= N
+                const bool tail = (2 * ks + t) >= nKT - 1;               // only the last key tile and the padding tile hold keys >= Lt
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[e], c, -lq));
-                    if (tail && (2 * ks + t) * 16 + g * 4 + e >= N) pr = 0.f;
+                    if (tail && (2 * ks + t) * 16 + g * 4 + e >= Lt) pr = 0.f;
                     ds[t][e] = pr * (dp[e] - dq);
                 }
             }
@@ -221,10 +296,10 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
         }
     }
 
-    // ---- phase B: dK, dV.  wave <- key tile; per query-tile pair: S, dP (D layout: rows q g*4+e, col key l15)
+    // ---- phase B: dK, dV.  wave <- key tile (prefix rows included); per query-tile pair: S, dP (D layout: rows q g*4+e, col key l15)
     for (int kt = wave; kt < nKT; kt += BWD_WAVES) {
         const int krow = kt * 16 + l15;
-        const bool kok = krow < N;
+        const bool kok = krow < Lt;
         uint4 kf[2], vf[2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -234,7 +309,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
         f32x4 dk[4], dv[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        for (int qs = 0; qs < nPair; ++qs) {
+        for (int qs = 0; qs < nQPair; ++qs) {
             f32x4 pr[2], ds[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -264,8 +339,16 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
                 dk[dt] = mfma_bf16(tr8(Qs, a, 16 * KP), db, dk[dt]);
             }
         }
-        if (kok) {
-            bf16_t* r = dqb + (size_t)krow * ld + g * 4;
+        if (PFX && krow < Lp) {                                           // a prefix key: fp32, no rounding step
+            float* rk = p.dpk + ((size_t)b * Lp + krow) * D + h * 64 + g * 4;
+            float* rv = p.dpv + ((size_t)b * Lp + krow) * D + h * 64 + g * 4;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                *reinterpret_cast<float4*>(rk + dt * 16) = make_float4(dk[dt][0] * p.scale, dk[dt][1] * p.scale, dk[dt][2] * p.scale, dk[dt][3] * p.scale);
+                *reinterpret_cast<float4*>(rv + dt * 16) = make_float4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+            }
+        } else if (kok) {
+            bf16_t* r = dqb + (size_t)(krow - Lp) * ld + g * 4;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 *reinterpret_cast<uint2*>(r + D + dt * 16) = make_uint2(pack_bf16x2(dk[dt][0] * p.scale, dk[dt][1] * p.scale),
@@ -276,11 +359,10 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma_kernel(AttnParam
     }
 }
 
-
-// Round 6, 197 / 222 tokens (NPAIR = 7).  Where the kernel above spends a 128 x 12-head launch (ablation: prologue alone 31 us -- it reads q, k, v, dO, O = 194 MB, HBM
-// rate, but in TEN dependent round trips with one workgroup per CU and nothing beside it; + phase A 41 us; + phase B 63 us; PMC: matrix pipes 18 % busy, 59 % of the wave
+// The plain form at 197 / 222 tokens (NPAIR = 7).  Where the kernel above in its first form spent a 128 x 12-head launch (ablation: prologue alone 31 us -- it read q, k, v, dO,
+// O = 194 MB at HBM rate, but from staging loops, in TEN dependent round trips with one workgroup per CU and nothing beside it; + phase A 41 us; + phase B 63 us; PMC: matrix pipes 18 % busy, 59 % of the wave
 // cycles parked in s_waitcnt, no bank conflicts; both phases sit at ~64 B/clk of LDS operand reads).  This form
-//   * makes every global read of the prologue in ONE round trip (151 -> 137 us on the evidence box);
+//   * makes every global read of the prologue in ONE round trip (151 -> 137 us on the evidence box; the kernel above has taken this prologue over since);
 //   * drops the masks of keys >= N in phase B, and in phase A in every key-tile pair but the last: a padded key's K and V rows are zero in LDS; in phase B it only
 //     feeds its own output column, which is never stored; in phase A its dS multiplies zero K rows, but it is not always finite (see tileA), so the last pair, which
 //     holds every padded key, keeps the mask (14 + 8 compare / select instructions per tile pair elsewhere).  Padded QUERIES still vanish through lse = +inf;
@@ -305,7 +387,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma3_kernel(AttnPara
     char* Gs = Vs + NP2 * KP;                                  // dO
     float* lse_s = reinterpret_cast<float*>(Gs + NP2 * KP);    // [NP2]  lse * log2(e)  (+inf beyond N -> P = 0)
     float* dq_s = lse_s + NP2;                                 // [NP2]  rowsum(dO * O)
-    // every global read of the prologue in ONE round trip (the kernel above makes ten: four staging loops of two trips each, then the lse / dO / O rows; with one
+    // every global read of the prologue in ONE round trip (four staging loops of two trips each, then the lse / dO / O rows, would make ten; with one
     // workgroup per CU nothing overlaps them): the four tiles' chunks and, for the thread that owns a query row, its lse and O row
     constexpr int CH = (NP2 * 8 + 64 * BWD_WAVES - 1) / (64 * BWD_WAVES);
     uint4 sq[CH], sk[CH], sv[CH], sg[CH], orow[8];
@@ -358,7 +440,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma3_kernel(AttnPara
     const float c = p.scale * 1.4426950408889634f;          // scores -> exp2 domain
 
     // ---- phase A: dQ.  wave <- query tile; per key-tile pair: S^T, dP^T (D layout: rows key g*4+e, col q l15).  The K / V fragments of the NEXT key tile and the
-    //      transposed K fragments of this pair are requested before this tile's arithmetic (the rounds 2-5 loop waited for each small group of reads where it used it:
+    //      transposed K fragments of this pair are requested before this tile's arithmetic (the plain loop of the kernel above waits for each small group of reads where it uses it:
     //      nine LDS round trips per pair)
     auto frag = [&](const char* A, const char* B, int row, uint4 (&fa)[2], uint4 (&fb)[2]) {
 #pragma unroll
@@ -490,24 +572,40 @@ __global__ __launch_bounds__(64 * BWD_WAVES) void attn_bwd_mfma3_kernel(AttnPara
 
 // ------------------------------------------------------------------------------------------------ generic path
 // One wave per (batch, head, row); lane = key while scoring, lane = d while accumulating.  Used for fp32 (parity mode)
-// and head sizes other than 64.  N <= 256, head dim <= 64.
-template <typename T>
+// and head sizes other than 64.  At most 256 keys [prefix | tokens], head dim <= 64.
+template <typename T, bool PFX>
+struct HeadPtrs {
+    const T *q, *k, *v, *pk, *pv;      // token rows (pitch 3D) and, in the prefix form, prefix rows (pitch D) of one (batch, head)
+    size_t ld, D;
+    int Lp, Lt;                        // prefix keys, all keys [prefix | tokens]
+    __device__ __forceinline__ HeadPtrs(const AttnParams& p, int b, int h, int hd) {
+        ld = 3 * (size_t)p.D; D = p.D; Lp = PFX ? p.Lp : 0; Lt = p.N + Lp;
+        q = static_cast<const T*>(p.qkv) + (size_t)b * p.N * ld + h * hd;
+        k = q + p.D; v = q + 2 * p.D;
+        pk = PFX ? static_cast<const T*>(p.pk) + (size_t)b * Lp * p.D + h * hd : nullptr;
+        pv = PFX ? static_cast<const T*>(p.pv) + (size_t)b * Lp * p.D + h * hd : nullptr;
+    }
+    __device__ __forceinline__ const T* key(int j) const { return PFX && j < Lp ? pk + (size_t)j * D : k + (size_t)(j - Lp) * ld; }
+    __device__ __forceinline__ const T* val(int j) const { return PFX && j < Lp ? pv + (size_t)j * D : v + (size_t)(j - Lp) * ld; }
+};
+
+template <typename T, bool PFX>
 __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(AttnParams p, int hd) {
     __shared__ float ps[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;                       // (b*H + h)*N + q
     if (row >= p.B * p.H * p.N) return;
     const int q = row % p.N, bh = row / p.N, h = bh % p.H, b = bh / p.H;
-    const size_t ld = 3 * (size_t)p.D;
-    const T* base = static_cast<const T*>(p.qkv) + (size_t)b * p.N * ld + h * hd;
-    const T* qp = base + (size_t)q * ld;
+    const HeadPtrs<T, PFX> hp(p, b, h, hd);
+    const int Lt = hp.Lt;
+    const T* qp = hp.q + (size_t)q * hp.ld;
     float s[4], mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int key = lane + 64 * i;
         s[i] = -INFINITY;
-        if (key < p.N) {
-            const T* kp = base + p.D + (size_t)key * ld;
+        if (key < Lt) {
+            const T* kp = hp.key(key);
             float a = 0.f;
             for (int d = 0; d < hd; ++d) a += Elem<T>::ld(qp + d) * Elem<T>::ld(kp + d);
             s[i] = a * p.scale;
@@ -517,7 +615,7 @@ __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(AttnParams p, int
     mx = wave_max(mx);
     float sum = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { s[i] = (lane + 64 * i) < p.N ? expf(s[i] - mx) : 0.f; sum += s[i]; }
+    for (int i = 0; i < 4; ++i) { s[i] = (lane + 64 * i) < Lt ? expf(s[i] - mx) : 0.f; sum += s[i]; }
     sum = wave_sum(sum);
 #pragma unroll
     for (int i = 0; i < 4; ++i) ps[wave][lane + 64 * i] = s[i] / sum;
@@ -525,21 +623,23 @@ __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(AttnParams p, int
     __builtin_amdgcn_wave_barrier();
     if (lane < hd) {
         float o = 0.f;
-        for (int key = 0; key < p.N; ++key) o += ps[wave][key] * Elem<T>::ld(base + 2 * p.D + (size_t)key * ld + lane);
+        for (int key = 0; key < Lt; ++key) o += ps[wave][key] * Elem<T>::ld(hp.val(key) + lane);
         Elem<T>::st(static_cast<T*>(p.out) + ((size_t)b * p.N + q) * p.D + h * hd + lane, o);
     }
 }
 
-// pass 1 (row = query): dsum[row] = sum_d dO*O; dQ.   pass 2 (row = key): dK, dV (deterministic, no atomics)
-template <typename T, int PASS>
+// pass 1 (row = query, B*H*N rows): dsum[row] = sum_d dO*O; dQ.   pass 2 (row = key, B*H*(Lp+N) rows): dK, dV of a token, dpk, dpv of a prefix row
+// (deterministic, no atomics)
+template <typename T, int PASS, bool PFX>
 __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(AttnParams p, int hd) {
     __shared__ float ps[4][256], ds_[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
-    if (row >= p.B * p.H * p.N) return;
-    const int r = row % p.N, bh = row / p.N, h = bh % p.H, b = bh / p.H;
-    const size_t ld = 3 * (size_t)p.D;
-    const T* base = static_cast<const T*>(p.qkv) + (size_t)b * p.N * ld + h * hd;
+    const int Lp = PFX ? p.Lp : 0, Lt = p.N + Lp, R = PASS == 1 ? p.N : Lt;
+    if (row >= p.B * p.H * R) return;
+    const int r = row % R, bh = row / R, h = bh % p.H, b = bh / p.H;
+    const HeadPtrs<T, PFX> hp(p, b, h, hd);
+    const size_t ld = hp.ld;
     const T* dob = static_cast<const T*>(p.dout) + (size_t)b * p.N * p.D + h * hd;
     const T* ob = static_cast<const T*>(p.out) + (size_t)b * p.N * p.D + h * hd;
     T* dqb = static_cast<T*>(p.dqkv) + (size_t)b * p.N * ld + h * hd;
@@ -554,11 +654,12 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(AttnParams p, int
         for (int i = 0; i < 4; ++i) {
             const int key = lane + 64 * i;
             float v = 0.f;
-            if (key < p.N) {
+            if (key < Lt) {
+                const T *kp = hp.key(key), *vp = hp.val(key);
                 float a = 0.f, dp = 0.f;
                 for (int d = 0; d < hd; ++d) {
-                    a += Elem<T>::ld(base + (size_t)r * ld + d) * Elem<T>::ld(base + p.D + (size_t)key * ld + d);
-                    dp += Elem<T>::ld(dob + (size_t)r * p.D + d) * Elem<T>::ld(base + 2 * p.D + (size_t)key * ld + d);
+                    a += Elem<T>::ld(hp.q + (size_t)r * ld + d) * Elem<T>::ld(kp + d);
+                    dp += Elem<T>::ld(dob + (size_t)r * p.D + d) * Elem<T>::ld(vp + d);
                 }
                 v = expf(a * p.scale - l) * (dp - dd);
             }
@@ -567,10 +668,11 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(AttnParams p, int
         __builtin_amdgcn_wave_barrier();
         if (lane < hd) {
             float a = 0.f;
-            for (int key = 0; key < p.N; ++key) a += ds_[wave][key] * Elem<T>::ld(base + p.D + (size_t)key * ld + lane);
+            for (int key = 0; key < Lt; ++key) a += ds_[wave][key] * Elem<T>::ld(hp.key(key) + lane);
             Elem<T>::st(dqb + (size_t)r * ld + lane, a * p.scale);
         }
     } else {
+        const T *kp = hp.key(r), *vp = hp.val(r);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = lane + 64 * i;
@@ -578,8 +680,8 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(AttnParams p, int
             if (q < p.N) {
                 float a = 0.f, dp = 0.f;
                 for (int d = 0; d < hd; ++d) {
-                    a += Elem<T>::ld(base + (size_t)q * ld + d) * Elem<T>::ld(base + p.D + (size_t)r * ld + d);
-                    dp += Elem<T>::ld(dob + (size_t)q * p.D + d) * Elem<T>::ld(base + 2 * p.D + (size_t)r * ld + d);
+                    a += Elem<T>::ld(hp.q + (size_t)q * ld + d) * Elem<T>::ld(kp + d);
+                    dp += Elem<T>::ld(dob + (size_t)q * p.D + d) * Elem<T>::ld(vp + d);
                 }
                 pv = expf(a * p.scale - lse[q]);
                 dv = pv * (dp - dsum[q]);
@@ -591,90 +693,120 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(AttnParams p, int
         if (lane < hd) {
             float ak = 0.f, av = 0.f;
             for (int q = 0; q < p.N; ++q) {
-                ak += ds_[wave][q] * Elem<T>::ld(base + (size_t)q * ld + lane);
+                ak += ds_[wave][q] * Elem<T>::ld(hp.q + (size_t)q * ld + lane);
                 av += ps[wave][q] * Elem<T>::ld(dob + (size_t)q * p.D + lane);
             }
-            Elem<T>::st(dqb + p.D + (size_t)r * ld + lane, ak * p.scale);
-            Elem<T>::st(dqb + 2 * p.D + (size_t)r * ld + lane, av);
+            if (PFX && r < Lp) {
+                p.dpk[((size_t)b * Lp + r) * p.D + h * hd + lane] = ak * p.scale;
+                p.dpv[((size_t)b * Lp + r) * p.D + h * hd + lane] = av;
+            } else {
+                Elem<T>::st(dqb + p.D + (size_t)(r - Lp) * ld + lane, ak * p.scale);
+                Elem<T>::st(dqb + 2 * p.D + (size_t)(r - Lp) * ld + lane, av);
+            }
         }
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host side
 bool force_generic() {
     static int v = -1;
     if (v < 0) { const char* e = clhip_cfg("ATTN_GENERIC"); v = (e && e[0] == '1') ? 1 : 0; }
     return v == 1;
 }
 
-int check(int B, int N, int H, int D, int dtype) {
-    CLHIP_CHECK_ARG(B > 0 && H > 0 && N > 0 && N <= 256 && D % H == 0 && D / H <= 64 && D % 8 == 0);
+// Lp = 0: the plain form (the prefix entry points refuse it themselves)
+int check(int B, int N, int Lp, int H, int D, int dtype) {
+    CLHIP_CHECK_ARG(B > 0 && H > 0 && N > 0 && N + Lp <= 256 && D % H == 0 && D / H <= 64 && D % 8 == 0);
     CLHIP_CHECK_ARG(dtype == CLHIP_BF16 || dtype == CLHIP_F32);
     return CLHIP_OK;
 }
+
+// one workgroup per (batch, head) of the MFMA kernel K with `smem` bytes of dynamic LDS; the first launch of each instantiation raises its limit to `cap`
+template <void (*K)(AttnParams)>
+void launch_head(int threads, size_t smem, int cap, hipStream_t s, const AttnParams& p) {
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    (void)once;
+    hipLaunchKernelGGL(K, dim3(p.B * p.H), dim3(threads), smem, s, p);
+}
+
+int pair_rows(int n) { return ((((n + 15) >> 4) + 1) & ~1) * 16; }      // n rows in 16-row tiles, the tiles rounded to a pair
+
+template <bool PFX>
+int launch_fwd(const AttnParams& p, int dtype, hipStream_t s) {
+    const int hd = p.D / p.H;
+    if (dtype == CLHIP_BF16 && hd == 64 && !force_generic()) {
+        const int nkt = (p.N + p.Lp + 15) >> 4;
+        const size_t smem = 2 * (size_t)pair_rows(p.N + p.Lp) * KP;
+        constexpr int cap = 2 * 256 * KP;
+        if (nkt == 13) launch_head<attn_fwd_mfma_kernel<13, PFX>>(256, smem, cap, s, p);
+        else if (nkt == 14) launch_head<attn_fwd_mfma_kernel<14, PFX>>(256, smem, cap, s, p);
+        else launch_head<attn_fwd_mfma_kernel<0, PFX>>(256, smem, cap, s, p);
+    } else {
+        const int rows = p.B * p.H * p.N;
+        if (dtype == CLHIP_BF16) hipLaunchKernelGGL((attn_fwd_generic_kernel<bf16_t, PFX>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
+        else hipLaunchKernelGGL((attn_fwd_generic_kernel<float, PFX>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
+    }
+    CLHIP_LAUNCH_CHECK();
+    return CLHIP_OK;
+}
+
+template <bool PFX>
+int launch_bwd(const AttnParams& p, int dtype, hipStream_t s) {
+    const int hd = p.D / p.H, NQ2 = pair_rows(p.N), NK2 = pair_rows(p.N + p.Lp);
+    const size_t smem = 2 * (size_t)(NQ2 + NK2) * KP + 2 * NQ2 * sizeof(float);
+    constexpr size_t kLdsMax = 160 * 1024;       // Q, dO, K, V of one head must fit the CU's LDS (four 224-row tiles do, a 256-row tile among them does not); else generic path
+    if (dtype == CLHIP_BF16 && hd == 64 && smem <= kLdsMax && !force_generic()) {
+        // plain form at 197 / 222 tokens: the read-ahead kernel, unless ATTN_BWD=1 asks for the general one (looked up per call: the tests compare the two bit for bit)
+        bool general = PFX || NK2 != 224;
+        if (!general) { const char* v = clhip_cfg("ATTN_BWD"); general = v != nullptr && atoi(v) == 1; }
+        if (general) launch_head<attn_bwd_mfma_kernel<PFX>>(64 * BWD_WAVES, smem, (int)kLdsMax, s, p);
+        else launch_head<attn_bwd_mfma3_kernel<7>>(64 * BWD_WAVES, smem, (int)kLdsMax, s, p);
+    } else {
+        CLHIP_CHECK_ARG(p.dsum != nullptr);
+        const int rq = p.B * p.H * p.N, rk = p.B * p.H * (p.N + p.Lp);      // pass 1: a wave per query, pass 2: a wave per key
+        if (dtype == CLHIP_BF16) {
+            hipLaunchKernelGGL((attn_bwd_generic_kernel<bf16_t, 1, PFX>), dim3((rq + 3) / 4), dim3(256), 0, s, p, hd);
+            hipLaunchKernelGGL((attn_bwd_generic_kernel<bf16_t, 2, PFX>), dim3((rk + 3) / 4), dim3(256), 0, s, p, hd);
+        } else {
+            hipLaunchKernelGGL((attn_bwd_generic_kernel<float, 1, PFX>), dim3((rq + 3) / 4), dim3(256), 0, s, p, hd);
+            hipLaunchKernelGGL((attn_bwd_generic_kernel<float, 2, PFX>), dim3((rk + 3) / 4), dim3(256), 0, s, p, hd);
+        }
+    }
+    CLHIP_LAUNCH_CHECK();
+    return CLHIP_OK;
+}
+
+float head_scale(int H, int D) { return 1.0f / sqrtf((float)(D / H)); }
 
 }  // namespace
 
 extern "C" int clhip_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, int D, int dtype, void* stream) {
     CLHIP_CHECK_ARG(qkv && out);
-    if (int rc = check(B, N, H, D, dtype)) return rc;
-    const int hd = D / H;
-    AttnParams p{qkv, out, lse, nullptr, nullptr, nullptr, B, N, H, D, 1.0f / sqrtf((float)hd)};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == CLHIP_BF16 && hd == 64 && !force_generic()) {
-        const int NP2 = ((((N + 15) >> 4) + 1) & ~1) * 16;
-        const size_t smem = 2 * (size_t)NP2 * KP;
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * KP);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel<14>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * KP);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * KP);
-            done = true;
-        }
-        const int nkt = (N + 15) >> 4;
-        if (nkt == 13) hipLaunchKernelGGL(attn_fwd_mfma_kernel<13>, dim3(B * H), dim3(256), smem, s, p);
-        else if (nkt == 14) hipLaunchKernelGGL(attn_fwd_mfma_kernel<14>, dim3(B * H), dim3(256), smem, s, p);
-        else hipLaunchKernelGGL(attn_fwd_mfma_kernel<0>, dim3(B * H), dim3(256), smem, s, p);
-    } else {
-        const int rows = B * H * N;
-        if (dtype == CLHIP_BF16) hipLaunchKernelGGL(attn_fwd_generic_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-        else hipLaunchKernelGGL(attn_fwd_generic_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-    }
-    CLHIP_LAUNCH_CHECK();
-    return CLHIP_OK;
+    if (int rc = check(B, N, 0, H, D, dtype)) return rc;
+    const AttnParams p{qkv, out, lse, nullptr, nullptr, nullptr, B, N, H, D, head_scale(H, D), nullptr, nullptr, nullptr, nullptr, 0};
+    return launch_fwd<false>(p, dtype, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int clhip_attn_bwd(const void* qkv, const void* out, const float* lse, const void* dout, void* dqkv, float* dsum_ws, int B, int N, int H,
                               int D, int dtype, void* stream) {
     CLHIP_CHECK_ARG(qkv && out && lse && dout && dqkv);
-    if (int rc = check(B, N, H, D, dtype)) return rc;
-    const int hd = D / H;
-    AttnParams p{qkv, const_cast<void*>(out), const_cast<float*>(lse), dout, dqkv, dsum_ws, B, N, H, D, 1.0f / sqrtf((float)hd)};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int NP2 = ((((N + 15) >> 4) + 1) & ~1) * 16;
-    const size_t smem = 4 * (size_t)NP2 * KP + 2 * NP2 * sizeof(float);
-    constexpr size_t kLdsMax = 160 * 1024;       // Q, K, V, dO of one head must fit the CU's LDS (N <= 240); else generic path
-    if (dtype == CLHIP_BF16 && hd == 64 && smem <= kLdsMax && !force_generic()) {
-        static bool done = false;
-        if (!done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma3_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-            done = true;
-        }
-        // ATTN_BWD=1: the rounds 2-5 kernel at every token count (looked up per call: the tests compare the two bit for bit); default: the round-6 form at 197 / 222 tokens
-        const char* v = clhip_cfg("ATTN_BWD");
-        if ((v != nullptr && atoi(v) == 1) || NP2 != 224) hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(B * H), dim3(64 * BWD_WAVES), smem, s, p);
-        else hipLaunchKernelGGL(attn_bwd_mfma3_kernel<7>, dim3(B * H), dim3(64 * BWD_WAVES), smem, s, p);
-    } else {
-        CLHIP_CHECK_ARG(dsum_ws != nullptr);
-        const int rows = B * H * N;
-        if (dtype == CLHIP_BF16) {
-            hipLaunchKernelGGL((attn_bwd_generic_kernel<bf16_t, 1>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-            hipLaunchKernelGGL((attn_bwd_generic_kernel<bf16_t, 2>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_generic_kernel<float, 1>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-            hipLaunchKernelGGL((attn_bwd_generic_kernel<float, 2>), dim3((rows + 3) / 4), dim3(256), 0, s, p, hd);
-        }
-    }
-    CLHIP_LAUNCH_CHECK();
-    return CLHIP_OK;
+    if (int rc = check(B, N, 0, H, D, dtype)) return rc;
+    const AttnParams p{qkv, const_cast<void*>(out), const_cast<float*>(lse), dout, dqkv, dsum_ws, B, N, H, D, head_scale(H, D), nullptr, nullptr, nullptr, nullptr, 0};
+    return launch_bwd<false>(p, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int clhip_attn_prefix_fwd(const void* qkv, const void* pk, const void* pv, void* out, float* lse, int B, int N, int Lp, int H, int D, int dtype,
+                                     void* stream) {
+    CLHIP_CHECK_ARG(qkv && pk && pv && out && Lp >= 1);
+    if (int rc = check(B, N, Lp, H, D, dtype)) return rc;
+    const AttnParams p{qkv, out, lse, nullptr, nullptr, nullptr, B, N, H, D, head_scale(H, D), pk, pv, nullptr, nullptr, Lp};
+    return launch_fwd<true>(p, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int clhip_attn_prefix_bwd(const void* qkv, const void* pk, const void* pv, const void* out, const float* lse, const void* dout, void* dqkv,
+                                     float* dpk, float* dpv, float* dsum_ws, int B, int N, int Lp, int H, int D, int dtype, void* stream) {
+    CLHIP_CHECK_ARG(qkv && pk && pv && out && lse && dout && dqkv && dpk && dpv && Lp >= 1);
+    if (int rc = check(B, N, Lp, H, D, dtype)) return rc;
+    const AttnParams p{qkv, const_cast<void*>(out), const_cast<float*>(lse), dout, dqkv, dsum_ws, B, N, H, D, head_scale(H, D), pk, pv, dpk, dpv, Lp};
+    return launch_bwd<true>(p, dtype, static_cast<hipStream_t>(stream));
 }

@@ -2,7 +2,7 @@
 
 Same constructor kwargs and hooks.  The backbone (a frozen ViT) gets a `CodaPromptPool` (backbone/vit.py; prompt.py:37-223): per step the device runs the
 query forward (no prefix, no gradient) -> one assembly launch for the five prompted layers (csrc/coda.hip) -> the forward whose blocks 0-4 attend over
-[prefix | tokens] (csrc/attn_prefix.hip inside csrc/vit_plan.hip) -> head + masked CE (clhip_linear_fwd, clhip_ce_window) -> ONE backbone backward that
+[prefix | tokens] (the prefix form of csrc/attn.hip inside csrc/vit_plan.hip) -> head + masked CE (clhip_linear_fwd, clhip_ce_window) -> ONE backbone backward that
 also fills the prefix gradients -> the assembly backward.  The trainer's default branch drives it (observe, then loss.backward()).
 
 The head is regrown in `before_task` as a fresh Linear of the new width with the old rows copied in (codaprompt.py:72-78), so the generator is consumed as

@@ -3,7 +3,7 @@
   * prefix attention: MultiHeadAttention.forward with `prompt` (transformer.py:169-197) -- per sample Lp key / value rows without a query in front of the
     token keys -- and `pack_prefix`, which writes the same computation as PLAIN attention over Lp + N tokens (the first Lp rows carry the prefix keys and
     values, an arbitrary query and zero dout: their dS is exactly zero, they contribute nothing to dK / dV), so that the bounds and references of
-    tests/vit_refs.py apply to csrc/attn_prefix.hip unchanged;
+    tests/vit_refs.py apply to the prefix form of csrc/attn.hip unchanged;
   * the prompt assembly, CodaPrompt.forward (prompt.py:158-220), on the literal formulas (F.normalize), gradients by autograd;
   * the prefixed ViT (VisionTransformer.forward with `prompt`, transformer.py:2272-2295, ViTZoo.forward, vit.py:120-138) on oracle.vit's blocks;
   * the method (core/model/codaprompt.py) with Adam.

@@ -1,4 +1,4 @@
-"""CODA-Prompt on the HIP ViT executor on a real MI355X: the executor's prefix mode (csrc/vit_plan.hip with csrc/attn_prefix.hip), the plugin
+"""CODA-Prompt on the HIP ViT executor on a real MI355X: the executor's prefix mode (csrc/vit_plan.hip with the prefix form of csrc/attn.hip), the plugin
 (model/codaprompt.py, backbone/vit.py with csrc/coda.hip) against tests/golden/coda_tiny.npz, and a run through the product Trainer.
 
 Executor tolerances are the numbers the suite already holds this executor to (tests/test_vit_parity_gpu.py): block activations 1e-4 in f32 and 4e-2 in bf16

@@ -1,17 +1,21 @@
-"""csrc/attn_prefix.hip through the C ABI on the MI355X, against the references and bounds tests/test_vit_ops_kernels_gpu.py holds csrc/attn.hip to.
+"""The prefix form of csrc/attn.hip (clhip_attn_prefix_fwd / _bwd) through the C ABI on the MI355X, against the references and bounds
+tests/test_vit_ops_kernels_gpu.py holds the plain form to; at the end, the two forms against each other.
 
 No reference or bound of its own: prefix attention over (N, Lp) IS plain attention over Lp + N tokens whose first Lp rows have keys and values, an
 arbitrary query and zero dout (their dS is exactly zero, they contribute nothing to dK / dV; tests/test_coda_cpu.py checks the identity in fp64).  Every
 case builds that packed input, calls vit_refs.attn_ref / attn_logit_abs / attn_cancel_bound on it and holds the kernels to the bounds of
 `run_attention` there, with its u, v rule (eps_o = 2^-9 in the bf16 modes, eps_ds = 2^-9 where dS is packed to bf16 for the MFMA, T 2^-24 otherwise).
 Each tensor is judged per (batch, head) on the rows the kernel produces, relative to the max|ref| of THOSE rows (never looser than the packed block's).
-dpk / dpv are fp32: their bound is the dk / dv bound without the final bf16 store step (half a bf16 ulp, 2^-9, off the relative part)."""
+dpk / dpv are fp32: their bound is the dk / dv bound without the final bf16 store step (half a bf16 ulp, 2^-9, off the relative part).
+
+Both forms are instantiations of the same kernels, so the last section runs clhip_attn_fwd / _bwd on the packed form itself (T = Lp + N tokens) and
+holds the token rows of the two entry-point families to each other (see test_plain_and_prefix_forms_agree)."""
 import pytest
 import torch
 
 import vit_refs as V
 from vit_refs import U, larger
-from test_vit_ops_kernels_gpu import CODE, DEV, GUARD, blocked, check, dev, guard_ok, measure, nan_out, p, st
+from test_vit_ops_kernels_gpu import CODE, DEV, GUARD, TD, blocked, check, dev, guard_ok, measure, nan_out, p, st
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +55,32 @@ def launch(qkv, pk, pv, dout, B, N, Lp, H, hd, dt):
     return (q_, k_, v_, do_), out, out2, lse, dqkv, dpk, dpv, dsum
 
 
+def references(big, bd, B, N, Lp, H, hd, dt):
+    """fp64 reference of the packed form cut to the rows the prefix kernels produce: {tensor: (ref, relative bound, elementwise extra)} for out, dq, dk, dv
+    (token rows) and dpk, dpv (prefix rows), the conditioning of the token queries' exponent [B,H,N], and the whole lse reference [B,H,T]"""
+    T = N + Lp
+    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = V.attn_ref(big, bd, B, T, H, hd)
+    assert float(ref_dq[:, :, :Lp].abs().max()) == 0.0                       # zero dout: the prefix rows' queries get nothing, as the kernel assumes
+    labs = V.attn_logit_abs(big, B, T, H, hd)[:, :, Lp:]                     # [B,H,N]: the token queries
+    cond = hd * U * labs
+    bf = dt == "bf16"
+    mfma = bf and hd == 64
+    cq, ck = V.attn_cancel_bound(big, bd, B, T, H, hd, 2.0 ** -9 if bf else U, 2.0 ** -9 if mfma else T * U)
+
+    def amax(t):
+        return t.abs().amax(dim=(-1, -2), keepdim=True)
+    tok, pre = (lambda t: t[:, :, Lp:]), (lambda t: t[:, :, :Lp])
+    cmax = cond.amax(-1)[..., None, None]
+    store = 2.0 ** -9 if bf else 0.0                                          # the bf16 store step dpk / dpv do not have
+    bounds = {"out": (tok(ref_o), V.ATTN_OUT[dt], cond[..., None] * amax(tok(ref_o)).expand_as(tok(ref_o))),
+              "dq": (tok(ref_dq), V.ATTN_GRAD[dt], tok(cq) + cond[..., None] * amax(tok(ref_dq))),
+              "dk": (tok(ref_dk), V.ATTN_GRAD[dt], tok(ck) + cmax * amax(tok(ref_dk))),
+              "dv": (tok(ref_dv), V.ATTN_GRAD[dt], (cmax * amax(tok(ref_dv))).expand_as(tok(ref_dv))),
+              "dpk": (pre(ref_dk), V.ATTN_GRAD[dt] - store, pre(ck) + cmax * amax(pre(ref_dk))),
+              "dpv": (pre(ref_dv), V.ATTN_GRAD[dt] - store, (cmax * amax(pre(ref_dv))).expand_as(pre(ref_dv)))}
+    return bounds, cond, ref_lse
+
+
 def run_prefix(big, bd, B, N, Lp, H, hd, dt, tag):
     """forward (with and without lse), backward, zero-dout backward; every output against the fp64 reference of the packed form per (batch, head)"""
     D, T = H * hd, N + Lp
@@ -62,28 +92,13 @@ def run_prefix(big, bd, B, N, Lp, H, hd, dt, tag):
     assert torch.equal(out[:B * N].view(bits), out2[:B * N].view(bits))
     for t in (out[:B * N], lse[:B * H * N], dqkv[:B * N], dpk[:B * Lp], dpv[:B * Lp]):
         assert bool(torch.isfinite(t.float()).all()), tag
-    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = V.attn_ref(big, bd, B, T, H, hd)
-    assert float(ref_dq[:, :, :Lp].abs().max()) == 0.0                       # zero dout: the prefix rows' queries get nothing, as the kernel assumes
-    labs = V.attn_logit_abs(big, B, T, H, hd)[:, :, Lp:]                     # [B,H,N]: the token queries
-    cond = hd * U * labs
-    bf = dt == "bf16"
-    mfma = bf and hd == 64
-    cq, ck = V.attn_cancel_bound(big, bd, B, T, H, hd, 2.0 ** -9 if bf else U, 2.0 ** -9 if mfma else T * U)
-    g_o = V.heads(V.f64(out[:B * N]), B, N, H, hd)
+    bounds, cond, ref_lse = references(big, bd, B, N, Lp, H, hd, dt)
     gq, gk, gv = V.split_qkv(V.f64(dqkv[:B * N]), B, N, H, hd)
-    gpk, gpv = V.heads(V.f64(dpk[:B * Lp]), B, Lp, H, hd), V.heads(V.f64(dpv[:B * Lp]), B, Lp, H, hd)
-
-    def amax(t):
-        return t.abs().amax(dim=(-1, -2), keepdim=True)
-    tok, pre = (lambda t: t[:, :, Lp:]), (lambda t: t[:, :, :Lp])
-    cmax = cond.amax(-1)[..., None, None]
-    store = 2.0 ** -9 if bf else 0.0                                          # the bf16 store step dpk / dpv do not have
-    blocked(f"{tag} out", g_o, tok(ref_o), V.ATTN_OUT[dt], cond[..., None] * amax(tok(ref_o)).expand_as(tok(ref_o)))
-    blocked(f"{tag} dq", gq, tok(ref_dq), V.ATTN_GRAD[dt], tok(cq) + cond[..., None] * amax(tok(ref_dq)))
-    blocked(f"{tag} dk", gk, tok(ref_dk), V.ATTN_GRAD[dt], tok(ck) + cmax * amax(tok(ref_dk)))
-    blocked(f"{tag} dv", gv, tok(ref_dv), V.ATTN_GRAD[dt], (cmax * amax(tok(ref_dv))).expand_as(tok(ref_dv)))
-    blocked(f"{tag} dpk", gpk, pre(ref_dk), V.ATTN_GRAD[dt] - store, pre(ck) + cmax * amax(pre(ref_dk)))
-    blocked(f"{tag} dpv", gpv, pre(ref_dv), V.ATTN_GRAD[dt] - store, (cmax * amax(pre(ref_dv))).expand_as(pre(ref_dv)))
+    got = {"out": V.heads(V.f64(out[:B * N]), B, N, H, hd), "dq": gq, "dk": gk, "dv": gv,
+           "dpk": V.heads(V.f64(dpk[:B * Lp]), B, Lp, H, hd), "dpv": V.heads(V.f64(dpv[:B * Lp]), B, Lp, H, hd)}
+    for nm in got:
+        blocked(f"{tag} {nm}", got[nm], *bounds[nm])
+    tok = lambda t: t[:, :, Lp:]
     g_lse = V.f64(lse[:B * H * N]).reshape(B, H, N)
     measure(f"{tag} lse abs", g_lse, tok(ref_lse))
     check(f"{tag} lse", g_lse, tok(ref_lse), larger(torch.full_like(tok(ref_lse), V.measured(V.LSE_ABS)), V.lse_floor(cond, T, tok(ref_lse))))
@@ -163,3 +178,69 @@ def test_prefix_attention_rejects_bad_arguments():
         torch.cuda.synchronize()
         assert bool(torch.isnan(out[:B * N].float()).all()) and bool(torch.isnan(dqkv[:B * N].float()).all()) and bool(torch.isnan(lse).all())
         assert bool(torch.isnan(dpk[:-1]).all()) and bool(torch.isnan(dpv[:-1]).all())
+
+
+# ------------------------------------------------------------------------------------------- the plain and the prefix form against each other
+def plain_launch(big, bd, B, T, H, hd, dt, general):
+    """clhip_attn_fwd / _bwd on the packed form; general: under ATTN_BWD=1 (the general MFMA backward also where attn_bwd_mfma3_kernel is the default)"""
+    D = H * hd
+    x_, d_ = dev(big, dt), dev(bd, dt)
+    out, dqkv = nan_out(B * T, D, dt), nan_out(B * T, 3 * D, dt)
+    lse, dsum = torch.full((B * H * T,), float("nan"), device=DEV), torch.empty(B * H * T, device=DEV)
+    call("clhip_attn_fwd", p(x_), p(out), p(lse), B, T, H, D, CODE[dt], st())
+    if general:
+        assert _lib.lib().clhip_config(b"ATTN_BWD", b"1") == 0
+    try:
+        call("clhip_attn_bwd", p(x_), p(out), p(lse), p(d_), p(dqkv), p(dsum), B, T, H, D, CODE[dt], st())
+        torch.cuda.synchronize()
+    finally:
+        if general:
+            _lib.lib().clhip_config(b"ATTN_BWD", None)
+    return out[:B * T].float().reshape(B, T, D), lse.reshape(B, H, T), dqkv[:B * T].reshape(B, T, 3, D)
+
+
+FORM_CASES = [("bf16", 64, 12, 4), ("bf16", 64, 13, 4), ("bf16", 64, 28, 4), ("bf16", 64, 29, 4), ("bf16", 64, 197, 4), ("bf16", 64, 197, 12),
+              ("bf16", 64, 223, 1), ("bf16", 64, 239, 1), ("f32", 64, 17, 4), ("bf16", 32, 17, 4)]
+
+
+@pytest.mark.parametrize("dt,hd,N,Lp", FORM_CASES)
+def test_plain_and_prefix_forms_agree(dt, hd, N, Lp):
+    """B = 2, H = 2.  clhip_attn_fwd / _bwd on the packed [B (Lp + N), 3D] input (the first Lp rows of dout zero) against clhip_attn_prefix_fwd / _bwd on its
+    split form.  One key tile (12,4); the prefix opens a second key tile over one query tile (13,4); exactly one tile pair (28,4); a second pair that is all
+    padding but one key (29,4); <13> and attn_bwd_mfma3_kernel against the general backward (197,4); 14 key tiles over 13 query tiles (197,12); T = 224,
+    the largest MFMA backward (223,1); T = 240 (239,1): forward <0> with 15 tiles, and the backward of both forms is generic (a 256-row tile among the four
+    exceeds the LDS rule); the generic kernels in both dtypes.  The plain backward runs twice, by default and under ATTN_BWD=1.
+    Token rows of out, lse, dq: VALUE-EQUAL (torch.equal on floats: -0.0 == 0.0).  A query is one MFMA column in both forms, meets the same keys in the same
+    tile order under the same mask (Lt = T), and the cross-lane reductions do not depend on the column or tile it sits in.
+    Generic kernels: dk, dv of the token rows and dpk / dpv against the packed form's first Lp key rows are value-equal too (the zero-dout rows add exact
+    zeros in front of an otherwise identical left-to-right sum); in bf16 the packed form's rows carry the bf16 store step dpk / dpv do not have, so dpk / dpv
+    are rounded to bf16 (the kernel's own round-to-nearest-even store) before the comparison.
+    MFMA dk, dv, dpk, dpv: the query tiles are grouped differently (shifted by Lp), so they are held to TWICE the bound run_prefix holds each tensor to
+    against the fp64 reference of the packed form: both sides are within that bound of the same reference."""
+    B, H, T, D = 2, 2, N + Lp, 2 * hd
+    big, bd = packed_inputs(B, N, Lp, H, hd, 1300 + 3 * N + Lp, dt)
+    qkv, pk, pv, dout = split(big, bd, B, N, Lp, D)
+    _, out, _, lse, dqkv, dpk, dpv, _ = launch(qkv, pk, pv, dout, B, N, Lp, H, hd, dt)
+    x_out, x_lse, x_dqkv = out[:B * N].float().reshape(B, N, D), lse[:B * H * N].reshape(B, H, N), dqkv[:B * N].reshape(B, N, 3, D)
+    x_pre = {1: dpk[:B * Lp].reshape(B, Lp, D), 2: dpv[:B * Lp].reshape(B, Lp, D)}
+    mfma = dt == "bf16" and hd == 64
+    bounds = references(big, bd, B, N, Lp, H, hd, dt)[0] if mfma else None
+    for general in (False, True):
+        tag = f"forms {dt} hd{hd} N={N} Lp={Lp} ATTN_BWD={int(general)}"
+
+        def within_twice(nm, a, b, rows):
+            """|a - b| to twice run_prefix's bound of tensor nm (blocked() is given a - b + ref against ref)"""
+            ref, rel, extra = bounds[nm]
+            diff = V.heads(V.f64(a), B, rows, H, hd) - V.heads(V.f64(b), B, rows, H, hd)
+            blocked(f"{tag} {nm} plain - prefix", diff + ref, ref, 2 * rel, 2 * extra)
+        p_out, p_lse, p_dqkv = plain_launch(big, bd, B, T, H, hd, dt, general)
+        assert torch.equal(p_out[:, Lp:], x_out), f"{tag} out"
+        assert torch.equal(p_lse[:, :, Lp:], x_lse), f"{tag} lse"
+        assert torch.equal(p_dqkv[:, Lp:, 0].float(), x_dqkv[:, :, 0].float()), f"{tag} dq"
+        for m, nm in ((1, "k"), (2, "v")):
+            if mfma:
+                within_twice("d" + nm, p_dqkv[:, Lp:, m], x_dqkv[:, :, m], N)
+                within_twice("dp" + nm, p_dqkv[:, :Lp, m], x_pre[m], Lp)
+            else:
+                assert torch.equal(p_dqkv[:, Lp:, m].float(), x_dqkv[:, :, m].float()), f"{tag} d{nm}"
+                assert torch.equal(p_dqkv[:, :Lp, m].float(), x_pre[m].to(TD[dt]).float()), f"{tag} dp{nm}"
