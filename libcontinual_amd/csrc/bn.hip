@@ -1,7 +1,9 @@
 // bn.hip -- BatchNorm2d (+ residual add + ReLU) forward / backward, global average pool, layout
 // conversion and conv-weight shadow preparation.  All HBM-bound streaming kernels: 16-byte (bf16x8)
 // or 32-byte (fp32x8) accesses per lane, coalesced along the NHWC channel axis, wavefront (64-lane)
-// reductions, per-block partials instead of atomics (deterministic).
+// reductions.  The partial-buffer path (clhip_bn_stats_finalize, clhip_bn_bwd) writes per-block partials and sums them in a fixed order: run-to-run
+// identical.  The accumulator path (the *_acc entries, clhip_add_stats, clhip_avgpool_bwd_bn_reduce) adds its per-block sums with fp64 atomics, whose
+// order is not fixed: equal to ~1e-16 relative, not bit for bit.
 //
 // Reference semantics: nn.BatchNorm2d(momentum=0.1, eps=1e-5) + F.relu + residual add,
 // core/model/backbone/resnet.py:296-316; nn.AvgPool2d(8) / AdaptiveAvgPool2d(1), :160, :344.
@@ -115,10 +117,18 @@ __global__ __launch_bounds__(256) void bn_apply_eval_kernel(const T* __restrict_
 }
 
 // ------------------------------------------------------------------------------------- backward
+// is the value, as it is stored in T, positive?  bf16: round-to-nearest-even sends a positive fp32 up to and including 2^-134 (half the smallest bf16
+// subnormal 2^-133; the tie goes to the even neighbour, 0) to +0 and everything above it to a positive value -- one compare, as cheap as `> 0.f`
+// (tests/test_bn_kernels_gpu.py::test_relu_mask_rule_at_the_storage_floor holds it to the stored y bit for bit)
+template <typename T> __device__ __forceinline__ bool stored_positive(float v);
+template <> __device__ __forceinline__ bool stored_positive<float>(float v) { return v > 0.f; }
+template <> __device__ __forceinline__ bool stored_positive<bf16_t>(float v) { return v > __uint_as_float(0x00008000u); }      // 2^-134
+
 // pass 1: per-channel partial sums of g = dy*mask and g*xhat over a slab of rows.
 // thread layout: cpr = C/8 chunk columns per row, rpi = 256/cpr rows per iteration.
 // RELU: 0 none, 1 mask = (y > 0), 2 mask recomputed from z -- units without a residual: y = max(fmaf(z, scale, shift), 0) with the
-// forward's own fp32 scale / shift expressions, so the sign test is bit-identical and the y tensor is not read at all
+// forward's own fp32 scale / shift expressions and the forward's own "positive as STORED" test (stored_positive<T>: in bf16 a positive fp32
+// value below 2^-134 is stored as +0), so the mask is bit-identical to reading y and the y tensor is not read at all; 3 the packed mask
 template <typename T, int RELU>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                                             const T* __restrict__ z, const float* __restrict__ mean,
@@ -173,7 +183,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
                 for (int e = 0; e < 8; ++e) {
                     float gg = g[u][e];
                     if (RELU == 1) gg = yy[u][e] > 0.f ? gg : 0.f;
-                    if (RELU == 2) gg = fmaf(zz[u][e], sc[e], sh[e]) > 0.f ? gg : 0.f;
+                    if (RELU == 2) gg = stored_positive<T>(fmaf(zz[u][e], sc[e], sh[e])) ? gg : 0.f;
                     if (RELU == 3) gg = (mk[u] >> e) & 1u ? gg : 0.f;
                     a1[e] += gg;
                     a2[e] += gg * (zz[u][e] - mu[e]) * is[e];
@@ -188,7 +198,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
     // values): all 256 threads take a slice of the rows first (a serial loop of 128 LDS reads was a third of the kernel there)
     const int nout = 2 * C;
     if (nout <= 128) {
-        const int nparts = 256 / nout;                       // power of two (C is)
+        // a power of two on the accumulator path; clhip_bn_bwd also admits C = 24, 40 (nparts = 5, 3): the threads left over then have prt >= nparts, sum rows
+        // that a thread with prt < nparts also sums, and write slots of red that the final loop (q < nparts) never reads
+        const int nparts = 256 / nout;
         const int out = threadIdx.x % nout, prt = threadIdx.x / nout;
         const int which = out / C, c = out - which * C;
         const int col = c >> 3, e = c & 7;
@@ -266,11 +278,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
         if (DRES == 2) store8<T>(dres + i * 8, rr);
     }
 }
-
-// is the value, as it is stored in T, positive?  (bf16: a positive fp32 below half the smallest bf16 subnormal rounds to +0)
-template <typename T> __device__ __forceinline__ bool stored_positive(float v);
-template <> __device__ __forceinline__ bool stored_positive<float>(float v) { return v > 0.f; }
-template <> __device__ __forceinline__ bool stored_positive<bf16_t>(float v) { return v > 0.f && (pack_bf16x2(v, 0.f) & 0xffffu) != 0u; }
 
 // ---------------------------------------------------------------------------- accumulator ("acc") variants
 // The per-layer finalize launches (bn_finalize, bn_bwd_finalize: 40 x ~6 us of a 3.3 ms ResNet-18 step) disappear when the
@@ -419,7 +426,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const T* __restri
             for (int e = 0; e < 8; ++e) {
                 float gg = g[u][e];
                 if (RELU == 1) gg = yy[u][e] > 0.f ? gg : 0.f;
-                if (RELU == 2) gg = fmaf(zz[u][e], gi[e], sh[e]) > 0.f ? gg : 0.f;
+                if (RELU == 2) gg = stored_positive<T>(fmaf(zz[u][e], gi[e], sh[e])) ? gg : 0.f;
                 if (RELU == 3) gg = (mk[u] >> e) & 1u ? gg : 0.f;
                 const float xh = (zz[u][e] - mu[e]) * is[e];
                 o[e] = gi[e] * (gg - k0[e] - xh * k1[e]);
