@@ -275,9 +275,30 @@ int clhip_plan_backward(clhip_plan*, const float* dfeat, const float* params, co
  * the data-parallel host start the all-reduce of the deepest layers' gradients (the tail of the flat gradient buffer: the
  * parameters are laid out in unit order) while the backward of the shallower layers is still running. */
 int clhip_plan_num_units(const clhip_plan* p);
+/* tests: which branch of the executor's dispatch unit `unit` took in the plan's LAST forward (fwd_bits) and LAST backward (bwd_bits; units outside a
+ * clhip_plan_backward_range keep their earlier word).  Host-side bookkeeping only: no device work, nothing launched differently.  Either pointer may be NULL. */
+#define CLHIP_FORM_FWD_LAZY_INPUT 1u      /* the producer's BatchNorm + ReLU applied on this convolution's operand load */
+#define CLHIP_FORM_FWD_LAZY_RES_INPUT 2u  /* ... of a block's last unit (+ residual), this launch writing the activation and its packed mask */
+#define CLHIP_FORM_FWD_WRITE_THROUGH 4u   /* ... on the patch landed in LDS (BN_INPUT_WT) */
+#define CLHIP_FORM_FWD_PAIR 8u            /* a down-sampling entry's two convolutions as one launch (on both units) */
+#define CLHIP_FORM_FWD_EVAL_LAZY 16u      /* eval forward: the producer's running-statistics BatchNorm applied on the operand load */
+#define CLHIP_FORM_BWD_BOTH 1u            /* dgrad and weight gradient as one launch */
+#define CLHIP_FORM_BWD_BN_GRAD 2u         /* ... which also applies the unit's BatchNorm backward on its operand loads (dz never written) */
+#define CLHIP_FORM_BWD_BN_GRAD_RES 4u     /* ... and writes the residual gradient from the packed mask */
+#define CLHIP_FORM_BWD_LAZY_INPUT 8u      /* the weight gradient's operand rebuilt from the producer's z (lazy activation) */
+#define CLHIP_FORM_BWD_EPILOGUE_SUMS 16u  /* the unit's BatchNorm-backward sums came from the launch that completed its dy (dgrad / pooling epilogue) */
+#define CLHIP_FORM_BWD_PAIR_DGRAD 32u     /* a down-sampling entry's two input gradients as one launch (on both units) */
+#define CLHIP_FORM_BWD_PAIR_BN_SUMS 64u   /* ... which also reduced the producer's BatchNorm-backward sums */
+#define CLHIP_FORM_BWD_WGRAD_PAIR 128u    /* ... and their two weight gradients as one launch (on both units) */
+#define CLHIP_FORM_BWD_SIDE_STREAM 256u   /* the weight gradient ran on the side stream */
+#define CLHIP_FORM_BWD_BRANCH 512u        /* the whole unit ran on the branch stream */
+#define CLHIP_FORM_BWD_EVENT_HOOK 1024u   /* the BatchNorm-backward launch completed the dz event itself */
+#define CLHIP_FORM_BWD_POOL_FUSED 2048u   /* (last unit) the pooling's backward reduced its BatchNorm-backward sums */
+int clhip_plan_unit_forms(const clhip_plan* p, int unit, unsigned* fwd_bits, unsigned* bwd_bits);
 int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, const float* params, const void* shadow, void* workspace,
                               float* grads, int unit_hi, int unit_lo, void* stream);
-/* debugging / tests: copy activation `idx` (0=input) as fp32 NCHW; which: 0 = y, 1 = pre-BN z (idx>=1), 2 = dy.
+/* debugging / tests: copy activation `idx` (0=input) as fp32 NCHW; which: 0 = y, 1 = pre-BN z (idx>=1), 2 = dy,
+ * 3 = the pre-pool z of the max-pool stem unit at its own size [N, C, Ho, Wo] (which = 1 is refused there: another shape than the activation).
  * Not every intermediate is written by the fast paths.  An activation whose BatchNorm the consumer applies on its operand load (training: the first convolution
  * of a block, also inside a stage-level run of stage_train.hip; eval: EVAL_LAZY) is REBUILT here from its z and coefficients by the apply launch the eager path
  * would have made -- which is why `workspace` is written to despite the const, and why the call must not be made between a forward and its backward on another

@@ -128,6 +128,7 @@ _PROTOS = {
     "clhip_plan_forward_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
     "clhip_plan_backward": (_i, [_p, _p, _p, _p, _p, _p, _p]),
     "clhip_plan_num_units": (_i, [_p]),
+    "clhip_plan_unit_forms": (_i, [_p, _i, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "clhip_plan_backward_range": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "clhip_plan_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
     "clhip_linear_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -131,6 +131,7 @@ struct clhip_plan {
     hipStream_t xch_stream = nullptr;   // the stream of the last such launch (two of them must never be in flight on two streams: see stage_train_serialize)
     bool xch_used = false;
     long long st_fwd_launches = 0, st_bwd_launches = 0;      // stage-level training launches so far (clhip_plan_stage_info)
+    std::vector<unsigned> form_fwd, form_bwd;   // per unit: the CLHIP_FORM_* branches its last forward / backward took (clhip_plan_unit_forms; host bookkeeping only)
     int feat_dim;
     bool side_ok;            // some unit's weight gradient is big enough for the side stream to pay (see clhip_plan_backward_range)
     int pool_win;            // 0: global average pool, else nn.AvgPool2d(pool_win) + NCHW flatten
@@ -369,6 +370,8 @@ extern "C" clhip_plan* clhip_plan_create_ex(const clhip_unit_desc* units, int n_
     const long long fuse_max_m = clhip_cfg("BN_FUSE_MAX_M") ? atoll(clhip_cfg("BN_FUSE_MAX_M")) : ((fe == nullptr && p->side_ok) ? 16384 : (1ll << 62));
     p->bwd_sums_ready.assign(p->units.size(), 0);
     p->mask_stale.assign(p->units.size(), 0);
+    p->form_fwd.assign(p->units.size(), 0u);
+    p->form_bwd.assign(p->units.size(), 0u);
     for (int i = 0; i < n_units; ++i) {
         Unit& u = p->units[i];
         u.fuse_src_bn = false;
@@ -876,6 +879,7 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
     double* acc = reinterpret_cast<double*>(ws + p->acc_off);
     const bool use_acc = training && p->use_acc;
     std::fill(p->bwd_sums_ready.begin(), p->bwd_sums_ready.end(), 0);
+    std::fill(p->form_fwd.begin(), p->form_fwd.end(), 0u);
     {
         const int64_t npix = (int64_t)p->N * p->H * p->W;
         const unsigned lb = (unsigned)((npix + 255) / 256);
@@ -1024,6 +1028,7 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
                 TRY(clhip_conv_fwd_acc_bn_input_wt(ws + a.z_off, &bi, &rs, sh + u.sh_fwd, ws + u.z_off, acc + u.a_fwd, u.rep_fwd, p->N, u.H, u.W, u.cin_pad, u.d.cout,
                                                    u.d.ksize, u.d.stride, u.d.pad, p->dtype, us));
                 p->wt_pending[u.wt_from] = 0;
+                p->form_fwd[i] |= CLHIP_FORM_FWD_WRITE_THROUGH;
             } else if (u.res_lazy_from >= 0 && p->res_pending[u.res_lazy_from]) {
                 // the producer is a block's last unit: its BatchNorm + residual add + ReLU happen on this convolution's operand load, and this launch
                 // writes the activation and the packed mask for the readers that follow
@@ -1038,13 +1043,16 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
                 TRY(clhip_conv_fwd_acc_bn_res_input(ws + a.z_off, &bi, &rs, sh + u.sh_fwd, ws + u.z_off, acc + u.a_fwd, u.rep_fwd, p->N, u.H, u.W, u.cin_pad,
                                                     u.d.cout, u.d.ksize, u.d.stride, u.d.pad, p->dtype, us));
                 p->res_pending[u.res_lazy_from] = 0;
+                p->form_fwd[i] |= CLHIP_FORM_FWD_LAZY_RES_INPUT;
             } else if (u.fpair && u.d.ksize == 1 && fwd_pair_done == u.pair) {
                 // z and the statistics of this shortcut came out of its 3x3 partner's launch
+                p->form_fwd[i] |= CLHIP_FORM_FWD_PAIR;
             } else if (u.fpair && u.d.ksize == 3 && !br_on && !on_br && !u.raw_src) {
                 const Unit& sc = p->units[u.pair];
                 TRY(clhip_conv_fwd_acc_pair(in, sh + u.sh_fwd, sh + sc.sh_fwd, ws + u.z_off, ws + sc.z_off, acc + u.a_fwd, u.rep_fwd, acc + sc.a_fwd, sc.rep_fwd, p->N, u.H,
                                             u.W, u.cin_pad, u.d.cout, p->dtype, us));
                 fwd_pair_done = (int)i;
+                p->form_fwd[i] |= CLHIP_FORM_FWD_PAIR;
             } else if (u.lazy_from >= 0 && p->lazy_live[u.lazy_from]) {
                 // the producer's BatchNorm + ReLU happen on this convolution's operand load: scale / shift, the saved statistics and the running
                 // statistics of the producer are this launch's by-products
@@ -1055,6 +1063,7 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
                 bi.mean = fr + a.f_mean; bi.invstd = fr + a.f_invstd; bi.coef = fr + a.f_scale;
                 TRY(clhip_conv_fwd_acc_bn_input(ws + a.z_off, &bi, sh + u.sh_fwd, ws + u.z_off, acc + u.a_fwd, u.rep_fwd, p->N, u.H, u.W, u.cin_pad, u.d.cout,
                                                 u.d.ksize, u.d.stride, u.d.pad, p->dtype, us));
+                p->form_fwd[i] |= CLHIP_FORM_FWD_LAZY_INPUT;
             } else {
                 TRY(clhip_conv_fwd_acc(in, sh + u.sh_fwd, ws + u.z_off, acc + u.a_fwd, u.rep_fwd, p->N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize,
                                        u.d.stride, u.d.pad, p->dtype, us));
@@ -1122,7 +1131,9 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
                 TRY(clhip_conv_fwd_acc_bn_res_input(ws + a.z_off, &bi, &rs, sh + u.sh_fwd, ws + u.z_off, nullptr, 1, p->N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize,
                                                     u.d.stride, u.d.pad, p->dtype, stream));
                 p->res_pending[u.res_lazy_from] = 0;
+                p->form_fwd[i] |= CLHIP_FORM_FWD_EVAL_LAZY;
             } else if (u.lazy_from >= 0 && p->lazy_live[u.lazy_from]) {
+                p->form_fwd[i] |= CLHIP_FORM_FWD_EVAL_LAZY;
                 const Unit& a = p->units[u.lazy_from];
                 const clhip_bn_input bi = eval_bi(a);
                 TRY(clhip_conv_fwd_acc_bn_input(ws + a.z_off, &bi, sh + u.sh_fwd, ws + u.z_off, nullptr, 1, p->N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize, u.d.stride,
@@ -1175,6 +1186,14 @@ extern "C" int clhip_plan_forward_ex(clhip_plan* p, const float* x, const float*
 
 extern "C" int clhip_plan_num_units(const clhip_plan* p) { return p ? (int)p->units.size() : 0; }
 
+// host bookkeeping only: which branches of the dispatch above / below unit `unit` took in the plan's last forward and last backward (CLHIP_FORM_* bits)
+extern "C" int clhip_plan_unit_forms(const clhip_plan* p, int unit, unsigned* fwd_bits, unsigned* bwd_bits) {
+    CLHIP_CHECK_ARG(p && unit >= 0 && unit < (int)p->units.size());
+    if (fwd_bits) *fwd_bits = p->form_fwd[unit];
+    if (bwd_bits) *bwd_bits = p->form_bwd[unit];
+    return CLHIP_OK;
+}
+
 extern "C" int clhip_plan_backward(clhip_plan* p, const float* dfeat, const float* params, const void* shadow, void* workspace,
                                    float* grads, void* stream) {
     CLHIP_CHECK_ARG(p);
@@ -1188,6 +1207,7 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
     char* ws = static_cast<char*>(workspace);
     const char* sh = static_cast<const char*>(shadow);
     float* fr = reinterpret_cast<float*>(ws + p->f_base);
+    for (int i = unit_lo; i < unit_hi; ++i) p->form_bwd[i] = 0u;
     // the pooling's backward inside the last run's stage-level launch (stage_train.hip: the gradient of the run's output is dfeat / (H W), formed in registers)
     bool pool_in_stage = false;
     {
@@ -1216,6 +1236,7 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
                 TRY(clhip_avgpool_bwd_bn_reduce(dfeat, ws + last.dy_off, ws + lu.z_off, lu.relu ? ws + last.y_off : nullptr, fr + lu.f_mean, fr + lu.f_invstd,
                                                 reinterpret_cast<double*>(ws + p->acc_off) + lu.a_bwd, lu.rep_bwd, p->N, last.H * last.W, last.C, p->dtype, stream));
                 p->bwd_sums_ready[p->units.size() - 1] = 1;
+                p->form_bwd[p->units.size() - 1] |= CLHIP_FORM_BWD_POOL_FUSED;
             } else TRY(clhip_avgpool_bwd(dfeat, ws + last.dy_off, p->N, last.H * last.W, last.C, p->dtype, stream));
         }
     }
@@ -1390,6 +1411,7 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
             //      gradient on the branch stream, beside the main path's next unit (which shares nothing with it but the gradient of their
             //      common input activation: this branch writes it first, the main path joins before it accumulates)
             const int slot = u.branch;
+            p->form_bwd[i] |= CLHIP_FORM_BWD_BRANCH;
             (void)hipStreamWaitEvent(p->br, p->bfork_ev[slot], 0);            // its dy = the residual gradient written by the consumer's BatchNorm backward
             p->bfork_ev[slot] = nullptr;
             if (p->wg_pending[k]) { (void)hipStreamWaitEvent(p->br, p->ev_wg[k], 0); p->wg_pending[k] = false; }      // the last reader of this dz buffer
@@ -1425,6 +1447,8 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
         static const bool ev_in_launch = clhip_cfg("EVENT_RECORD") == nullptr;
         const bool hook = on_side && ev_in_launch && !u.no_bn && u.rep_bwd > 0 && !u.has_dzr;
         if (hook) clhip_bn_set_stop_event(p->ev_dz[k]);
+        if (hook) p->form_bwd[i] |= CLHIP_FORM_BWD_EVENT_HOOK;
+        if (on_side) p->form_bwd[i] |= CLHIP_FORM_BWD_SIDE_STREAM;
         // layers whose dgrad and weight gradient are both launches at their latency floor on this one stream: ONE launch for the two
         // (clhip_conv_dgrad_wgrad, conv3.hip: CifarResNet-32 stages 1 and 2) ...
         const bool both = !on_side && u.d.src != 0 && !u.raw_src && !(p->br_act >= 0 && u.d.src == p->br_act) &&
@@ -1439,6 +1463,9 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
                                 u.relu && !mask_from_y && u.cin_pad == u.d.cin &&                                 clhip_conv_bn_input_supported(p->N, u.H, u.W, u.cin_pad, u.d.cout, u.d.ksize, u.d.stride, u.d.pad, p->dtype);
         const bool stale = p->mask_stale[i] != 0;                  // its packed mask was not written (stage-level forward): the activation instead
         const bool bn_grad = bn_grad_ok && (dres == nullptr ? true : (u.mask_off != 0 && lazy_res_on && !stale));
+        if (both) p->form_bwd[i] |= CLHIP_FORM_BWD_BOTH;
+        if (!u.no_bn && u.rep_bwd > 0 && p->bwd_sums_ready[i]) p->form_bwd[i] |= CLHIP_FORM_BWD_EPILOGUE_SUMS;
+        if (bn_grad) p->form_bwd[i] |= dres != nullptr ? (CLHIP_FORM_BWD_BN_GRAD | CLHIP_FORM_BWD_BN_GRAD_RES) : CLHIP_FORM_BWD_BN_GRAD;
         if (u.no_bn || bn_grad) {
         } else if (((plan_skip() & 2) || ((plan_skip() & 8) && u.d.ksize == 1 && !u.relu)) && u.rep_bwd > 0) {         // timing ablation: no BatchNorm backward [8: of the shortcut units] (results invalid)
         } else if (u.rep_bwd > 0 && p->bwd_sums_ready[i]) {
@@ -1508,6 +1535,7 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
             bg.mean = fr + u.f_mean; bg.invstd = fr + u.f_invstd; bg.gamma = params + u.d.gamma_off; bg.beta = params + u.d.beta_off;
             bg.dgamma = grads + u.d.gamma_off; bg.dbeta = grads + u.d.beta_off;
             bg.relu_mask = dres != nullptr ? ws + u.mask_off : nullptr; bg.dres = dres; bg.dres_accumulate = u.dres_acc;
+            if (lazy_in) p->form_bwd[i] |= CLHIP_FORM_BWD_LAZY_INPUT;
             const Unit* la = lazy_in ? &p->units[u.lazy_from] : nullptr;       // its input is a lazy activation as well: x = z of that unit + its coefficients
             TRY(clhip_conv_dgrad_wgrad_bn_grad(la ? ws + la->z_off : in, la ? fr + la->f_scale : nullptr, &bg, sh + u.sh_dg, ws + src.dy_off, u.dx_acc,
                                                grads + u.d.w_off, ws + u.wg_own, prod ? ws + prod->z_off : nullptr, (prod && prod->relu) ? ws + src.y_off : nullptr,
@@ -1520,6 +1548,7 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
         if (both && u.lazy_from >= 0 && p->lazy_live[u.lazy_from]) {
             const Unit& a = p->units[u.lazy_from];                // x = relu(bn(z_a)) on the weight gradient's operand load, the producer's ReLU mask from z_a
             const bool red = u.fuse_src_bn;
+            p->form_bwd[i] |= CLHIP_FORM_BWD_LAZY_INPUT;
             TRY(clhip_conv_dgrad_wgrad_bn_input(ws + a.z_off, fr + a.f_scale, dz, sh + u.sh_dg, ws + src.dy_off, u.dx_acc, grads + u.d.w_off, ws + u.wg_own,
                                                 red ? fr + a.f_mean : nullptr, red ? fr + a.f_invstd : nullptr,
                                                 red ? reinterpret_cast<double*>(ws + p->acc_off) + a.a_bwd : nullptr, red ? a.rep_bwd : 1, p->N, u.H, u.W,
@@ -1539,8 +1568,10 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
         }
         if (pair_b && u.wpair) {
             // its weight gradient comes out of its 3x3 partner's launch (the next unit of this sweep)
+            p->form_bwd[i] |= CLHIP_FORM_BWD_WGRAD_PAIR;
         } else if (pair_on && u.pair >= 0 && u.wpair && u.d.ksize == 3 && pair_dz != nullptr) {
             const Unit& sc = p->units[u.pair];
+            p->form_bwd[i] |= CLHIP_FORM_BWD_WGRAD_PAIR;
             TRY(clhip_conv_wgrad_pair(in, dz, pair_dz, grads + u.d.w_off, grads + sc.d.w_off, ws + u.wg_own, ws + sc.wg_own, p->N, u.H, u.W, u.cin_pad, u.d.cout,
                                       p->dtype, wg_stream));
         } else if (!(plan_skip() & 4))
@@ -1566,8 +1597,10 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
             p->bwd_sums_ready[u.d.src - 1] = 1;
         } else if (pair_b) {
             pair_dz = dz;                                      // its partner is the next unit of this sweep
+            p->form_bwd[i] |= CLHIP_FORM_BWD_PAIR_DGRAD;
         } else if (pair_on && u.pair >= 0 && u.d.ksize == 3 && pair_dz != nullptr) {
             static const bool pfb_off = clhip_cfg("PAIR_BN_FUSE") != nullptr && atoi(clhip_cfg("PAIR_BN_FUSE")) == 0;
+            p->form_bwd[i] |= (u.pair_fuse_bn && !pfb_off) ? (CLHIP_FORM_BWD_PAIR_DGRAD | CLHIP_FORM_BWD_PAIR_BN_SUMS) : CLHIP_FORM_BWD_PAIR_DGRAD;
             if (u.pair_fuse_bn && !pfb_off) {
                 const Unit& prod = p->units[u.d.src - 1];
                 TRY(clhip_conv_dgrad_pair_bn_reduce(dz, sh + u.sh_pk, pair_dz, ws + src.dy_off, u.pair_acc, ws + prod.z_off, prod.relu ? ws + src.y_off : nullptr,
@@ -1599,8 +1632,13 @@ extern "C" int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, cons
 }
 
 extern "C" int clhip_plan_read_act(clhip_plan* p, const void* workspace, int idx, int which, float* out_nchw, void* stream) {
-    CLHIP_CHECK_ARG(p && workspace && out_nchw && idx >= 0 && idx < (int)p->acts.size() && which >= 0 && which <= 2);
+    CLHIP_CHECK_ARG(p && workspace && out_nchw && idx >= 0 && idx < (int)p->acts.size() && which >= 0 && which <= 3);
     CLHIP_CHECK_ARG(!(idx == 0 && which != 0));
+    if (which == 3) {                                       // the max-pool stem's z at its own (pre-pool) size
+        CLHIP_CHECK_ARG(p->units[idx - 1].maxpool);
+        const Unit& um = p->units[idx - 1];
+        return clhip_nhwc_to_nchw(static_cast<const char*>(workspace) + um.z_off, out_nchw, p->N, um.d.cout, um.Ho, um.Wo, p->dtype, stream);
+    }
     if (which == 1 && idx >= 1 && p->units[idx - 1].maxpool) {
         clhip_set_error("clhip_plan_read_act: activation %d is the max-pooled stem output; its pre-pool z has another shape", idx);
         return CLHIP_EINVAL;

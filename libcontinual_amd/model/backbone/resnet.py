@@ -620,7 +620,23 @@ class HipResNet(nn.Module):
         """tests: fp32 NCHW copy of activation `act` of the LAST forward (0 = padded input);
         which: 0 = y, 1 = pre-BN conv output z, 2 = gradient wrt y"""
         c = 8 if act == 0 else self._units[act - 1].cout
+        if which == 3:                                 # the max-pool stem's z at its own (pre-pool) size
+            state, u = self._last_state, self._units[act - 1]
+            N, _, H, W = state["shape"]
+            t = torch.empty(N, c, (H + 2 * u.pad - u.k) // u.stride + 1, (W + 2 * u.pad - u.k) // u.stride + 1, device=state["ws"].device, dtype=torch.float32)
+            call("clhip_plan_read_act", state["plan"], state["ws"].data_ptr(), act, 3, t.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return t
         return self._read_act(self._last_state, act, which, c)
+
+    def debug_unit_forms(self):
+        """tests: per unit the (forward, backward) CLHIP_FORM_* words of the last passes of the last forward's plan (clhip_plan_unit_forms)"""
+        import ctypes
+        out = []
+        for i in range(len(self._units)):
+            f, b = ctypes.c_uint(0), ctypes.c_uint(0)
+            call("clhip_plan_unit_forms", self._last_state["plan"], i, ctypes.byref(f), ctypes.byref(b))
+            out.append((f.value, b.value))
+        return out
 
     # deepcopy (teachers: lwf.py:49, icarl.py:172, lucir.py:87) must not share workspaces or plans
     def __deepcopy__(self, memo):
