@@ -792,8 +792,24 @@ int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const voi
 int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* const* pk, const void* const* pv);
 int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
                               float* const* d_lora_b, float* const* dpk, float* const* dpv, void* stream);
-/* debug/test: copy one saved activation of layer l (0 x_in, 1 qkv, 2 attn out, 3 x_mid, 4 GELU derivative of the mlp) to fp32 */
+/* debug/test: copy one saved tensor of layer l of the last forward to fp32: 0 x_in [M, D] (layer == depth: the last block's output), 1 qkv [M, 3D],
+ * 2 attn out, 3 x_mid, 4 GELU derivative of the mlp [M, mlp], 5 h1 = the LN1 output [M, D], 6 lse [B, H, N], 7 the LN1 statistics [2, M] (mean row, rstd
+ * row), 8 the LN2 statistics likewise, 9 the adapter's dropped hidden rows [M, R].  0..4 and 6..9 need a forward that saved for the backward; 5 needs h1 to
+ * have a region of its own (LoRA or SD-LoRA with a saving forward, or any forward with a Gram buffer): where it aliases the LN2 scratch the call is
+ * refused, as is 9 without adapters.  Host bookkeeping and one copy; nothing of a step changes. */
 int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream);
+/* debug/test: a gradient tap.  While buf != NULL every backward copies each buffer of its chain to fp32 in buf right after the launch that wrote it,
+ * on the caller's stream (the copy of dqkv is one more reader ahead of the next layer's writer on that stream: no new event).  With M = B * tokens of
+ * the last saved forward, in floats: [0, M D) = g after the pooled-LN backward; layer l's slots start at M D + l * stride, stride = M (mlp + 8 D) (+ M (R + D)
+ * with adapters), in this order: dbig [M, mlp] | with adapters: ad_dh [M, R], the adapter's output gradient g + dh Wd [M, D] | dtmp after the fc1 dgrad |
+ * g after the LN2 backward | dtmp after the proj dgrad [M, D each] | dqkv [M, 3D] | dtmp after the qkv dgrad | g after the LN1 backward [M, D each].
+ * Slots of launches a backward does not run are left untouched.  tap_floats: the size for the last saved forward (0: none).  A backward whose tap is
+ * smaller is refused.  set_tap(v, NULL, 0) switches it off. */
+int clhip_vit_set_tap(clhip_vit* v, float* buf, size_t floats);
+size_t clhip_vit_tap_floats(const clhip_vit* v);
+/* host bookkeeping of the last backward that passed its argument checks: did its leaves (LoRA / SD-LoRA weight gradients) run on the side stream, and the
+ * lowest layer it ran (the prefix-only backward stops at the lowest prefixed layer) */
+int clhip_vit_last_backward_info(const clhip_vit* v, int* side_stream_used, int* lowest_layer_run);
 
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline on the GPU.  store: uint8 [Nimg, H, W, 3] resident in HBM; index [B]: rows

@@ -204,6 +204,9 @@ _PROTOS = {
     "clhip_vit_forward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _i, _p, _i, _i, _p, _p, _p]),
     "clhip_vit_backward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p]),
     "clhip_vit_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
+    "clhip_vit_set_tap": (_i, [_p, _p, _sz]),
+    "clhip_vit_tap_floats": (_sz, [_p]),
+    "clhip_vit_last_backward_info": (_i, [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "clhip_vit_set_adapter_dropout": (_i, [_p, _p, _f]),
     "clhip_vit_backward_adapter": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _p]),
     "clhip_adapter_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _i, _i, _i, _i, _p]),

@@ -20,6 +20,7 @@ struct LayerShadow { size_t qkv_f, qkv_b, proj_f, proj_b, fc1_f, fc1_b, fc2_f, f
 
 struct Layout {          // byte offsets into the workspace for one (B, n_prompt, save) configuration
     int B, P, N, M, save;
+    bool h1_own;             // h1 has a region of its own (keep_h1, or bit 1 of the flags); else it aliases ln_out, which LN2 rewrites
     size_t patches, pe_out, ln_out, act, g, dtmp, dbig, dqkv, dsum, lora_ws, g2, ad_dh, ad_ws, sd_ws, total;
     std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse, ad_hd;   // per layer (x_in has depth+1 entries)
     std::vector<int> pf_lp;                  // prefix mode of the forward that filled this layout (empty = off): per layer the prefix length ...
@@ -50,7 +51,32 @@ struct clhip_vit {
     const float *sd_mag, *sd_inv;
     std::vector<int> pf_lp;                // prefix mode (clhip_vit_set_prefix): per layer the prefix length (empty = off) ...
     std::vector<const void*> pf_pk, pf_pv; // ... and the caller's buffers
+    float* tap;                            // gradient tap (clhip_vit_set_tap; nullptr = off): host bookkeeping and copies only
+    size_t tap_cap;
+    int info_side, info_lowest;            // what the last backward did (clhip_vit_last_backward_info; -1 = none yet)
 };
+
+// The tap's slot map for the layout of the last saved forward, in floats.  Slot 0 holds g after ln_pool_bwd [M, D]; layer l's slots follow at
+// M D + l * stride in the order of tap_slot_off: dbig [M, mlp] | ad_dh [M, R] | the adapter's output gradient [M, D] (both absent when R = 0) |
+// dtmp after the fc1 dgrad | g after the LN2 backward | dtmp after the proj dgrad [M, D each] | dqkv [M, 3D] | dtmp after the qkv dgrad | g after the
+// LN1 backward [M, D each].  A slot the backward does not write (a layer below the lowest one it runs) is left as the caller filled it.
+enum { TAP_DBIG = 0, TAP_AD_DH, TAP_AD_GX, TAP_DFC1, TAP_G_LN2, TAP_DPROJ, TAP_DQKV, TAP_DQKV_IN, TAP_G_LN1, TAP_SLOTS };
+static size_t tap_slot_floats(const clhip_vit* v, const Layout& L, int slot) {
+    const size_t M = L.M, D = v->d.dim, R = v->d.adapter_dim;
+    switch (slot) {
+        case TAP_DBIG: return M * v->d.mlp;
+        case TAP_AD_DH: return M * R;
+        case TAP_AD_GX: return R > 0 ? M * D : 0;
+        case TAP_DQKV: return M * 3 * D;
+        default: return M * D;
+    }
+}
+static size_t tap_slot_off(const clhip_vit* v, const Layout& L, int layer, int slot) {      // layer < 0: slot 0; slot == TAP_SLOTS: the layer's end
+    size_t stride = 0, in = 0;
+    for (int s = 0; s < TAP_SLOTS; ++s) { if (s < slot) in += tap_slot_floats(v, L, s); stride += tap_slot_floats(v, L, s); }
+    if (layer < 0) return 0;
+    return (size_t)L.M * v->d.dim + (size_t)layer * stride + in;
+}
 
 // `flags`: bit 0 = keep what the backward needs; bit 1 (CLHIP_VIT_KEEP_ATTN_IN) = keep every layer's attention input (LN1 output) until the
 // end of the forward -- the Gram pass multiplies all of them in one launch
@@ -90,6 +116,7 @@ static void make_layout(const clhip_vit* v, int B, int P, int flags, Layout& L) 
             L.st1[l] = L.st1[0]; L.st2[l] = L.st2[0]; L.lse[l] = L.lse[0];
         }
     }
+    L.h1_own = keep_h1 || (flags & 2);
     if ((flags & 2) && !keep_h1) {                       // one contiguous region, layer stride M * D elements
         const size_t base = take((size_t)d.depth * al(M * D * e));
         for (int l = 0; l < d.depth; ++l) L.h1[l] = base + (size_t)l * al(M * D * e);
@@ -148,6 +175,7 @@ extern "C" clhip_vit* clhip_vit_create(const clhip_vit_desc* desc, int dtype) {
     v->have_last = false;
     v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = 0.f;
     v->sd_terms = v->sd_sum = 0; v->sd_factors = nullptr; v->sd_mag = v->sd_inv = nullptr;
+    v->tap = nullptr; v->tap_cap = 0; v->info_side = v->info_lowest = -1;
     return v;
 }
 
@@ -168,6 +196,14 @@ extern "C" size_t clhip_vit_workspace_bytes(const clhip_vit* v, int B, int n_pro
 }
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != CLHIP_OK) return rc_; } while (0)
+
+static int vit_to_f32(const void* src, float* out, size_t n, int dtype, hipStream_t s) {
+    const int blocks = (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
+    if (dtype == CLHIP_BF16) hipLaunchKernelGGL(to_f32_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, (const bf16_t*)src, out, n);
+    else hipLaunchKernelGGL(to_f32_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)src, out, n);
+    CLHIP_LAUNCH_CHECK();
+    return CLHIP_OK;
+}
 
 extern "C" int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long long* seed, float p) {
     CLHIP_CHECK_ARG(v && v->d.adapter_dim > 0);
@@ -343,6 +379,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
     CLHIP_CHECK_ARG(dprompt_tokens == nullptr || L.P > 0);
     CLHIP_CHECK_ARG(d_lora_b == nullptr || d.lora_rank > 0);
     CLHIP_CHECK_ARG((dpk != nullptr) == !L.pf_lp.empty() && (dpk != nullptr) == (dpv != nullptr));
+    CLHIP_CHECK_ARG(v->tap == nullptr || v->tap_cap >= tap_slot_off(v, L, v->d.depth, 0));
     int lowest = 0;                                            // the lowest layer whose attention backward somebody needs
     if (dpk && !dprompt_tokens && !d_lora_b && !d_adapter && !d_sd)
         while (L.pf_lp[lowest] == 0) ++lowest;
@@ -378,19 +415,31 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
         lora_pending = true;
         return CLHIP_OK;
     };
+    // the tap: a copy of a chain buffer to fp32 on the caller's stream right after the launch that wrote it (one more reader ahead of the next writer)
+    auto tap = [&](const void* src, int layer, int slot) -> int {
+        if (!v->tap) return CLHIP_OK;
+        const size_t n = layer < 0 ? (size_t)M * D : tap_slot_floats(v, L, slot);
+        return n ? vit_to_f32(src, v->tap + tap_slot_off(v, L, layer, slot), n, dt, main_s) : CLHIP_OK;
+    };
+    v->info_side = side_on ? 1 : 0; v->info_lowest = -1;
     TRY(clhip_ln_pool_bwd(dfeat, ws + L.x_in[d.depth], P->norm_w, g, B, N, D, L.P > 0 ? L.P : 1, 1e-6f, dt, stream));
+    TRY(tap(g, -1, 0));
     for (int l = d.depth - 1; l >= 0; --l) {
         const clhip_vit_layer_params& p = P->layers[l];
         const LayerShadow& s = v->sh[l];
         const float* st1 = reinterpret_cast<const float*>(ws + L.st1[l]);
         const float* st2 = reinterpret_cast<const float*>(ws + L.st2[l]);
         // MLP branch: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
+        v->info_lowest = l;
         TRY(clhip_gemm_nt(g, sh + s.fc2_b, ws + L.dbig, nullptr, nullptr, ws + L.hpre[l], M, Hm, D, D, D, Hm, 0, Hm, EPI_MUL, dt, stream));
+        TRY(tap(ws + L.dbig, l, TAP_DBIG));
         if (R > 0) {
             // adapter branch: g is dL/dx_out here (the fc2 dgrad above has read it, LN2's += comes below).  g2 = g + dh Wd, then the two buffers
             // swap roles: the chain goes on in g2 and the weight gradient still finds dL/dx_out in the old one.  One stream: one summation order.
             CLHIP_CHECK_ARG(p.ad_down_w && p.ad_up_w);
             TRY(clhip_adapter_bwd(g, ws + L.ad_hd[l], p.ad_up_w, p.ad_down_w, ws + L.ad_dh, g2, v->last_p, d.adapter_scale, M, D, R, dt, stream));
+            TRY(tap(ws + L.ad_dh, l, TAP_AD_DH));
+            TRY(tap(g2, l, TAP_AD_GX));
             if (d_adapter) {
                 float* const* ga = d_adapter + 4 * l;
                 CLHIP_CHECK_ARG(ga[0] && ga[1] && ga[2] && ga[3]);
@@ -400,9 +449,12 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
             char* t = g; g = g2; g2 = t;
         }
         TRY(clhip_gemm_nt(ws + L.dbig, sh + s.fc1_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, Hm, Hm, Hm, D, 0, 0, EPI_NONE, dt, stream));
+        TRY(tap(ws + L.dtmp, l, TAP_DFC1));
         TRY(clhip_ln_bwd(ws + L.dtmp, ws + L.x_mid[l], p.ln2_w, st2, st2 + M, g, M, D, dt, stream));
+        TRY(tap(g, l, TAP_G_LN2));
         // attention branch: x_mid = x_in + proj(attn(qkv(LN1(x_in))))
         TRY(clhip_gemm_nt(g, sh + s.proj_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, D, D, D, D, 0, 0, EPI_NONE, dt, stream));
+        TRY(tap(ws + L.dtmp, l, TAP_DPROJ));
         if (lora_pending) { (void)hipStreamWaitEvent(main_s, v->ev_l, 0); lora_pending = false; }     // the previous layer's dB has read dqkv
         if (dpk && L.pf_lp[l] > 0) {
             CLHIP_CHECK_ARG(dpk[l] && dpv[l]);
@@ -411,6 +463,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
         } else
             TRY(clhip_attn_bwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<const float*>(ws + L.lse[l]), ws + L.dtmp, ws + L.dqkv,
                                reinterpret_cast<float*>(ws + L.dsum), B, N, d.heads, D, dt, stream));
+        TRY(tap(ws + L.dqkv, l, TAP_DQKV));
         if (d_lora_b) {
             CLHIP_CHECK_ARG(p.lora_a_k && p.lora_a_v && d_lora_b[2 * l] && d_lora_b[2 * l + 1]);
             TRY(leaf([&](void* ls) {
@@ -429,7 +482,9 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
         }
         if (l == lowest && dprompt_tokens == nullptr) break;      // nothing below the first block (or the lowest prefixed one) needs a gradient
         TRY(clhip_gemm_nt(ws + L.dqkv, sh + s.qkv_b, ws + L.dtmp, nullptr, nullptr, nullptr, M, D, 3 * D, 3 * D, 3 * D, D, 0, 0, EPI_NONE, dt, stream));
+        TRY(tap(ws + L.dtmp, l, TAP_DQKV_IN));
         TRY(clhip_ln_bwd(ws + L.dtmp, ws + L.x_in[l], p.ln1_w, st1, st1 + M, g, M, D, dt, stream));
+        TRY(tap(g, l, TAP_G_LN1));
     }
     if (dprompt_tokens) TRY(clhip_vit_prompt_grad(g, dprompt_tokens, B, N, L.P, D, dt, stream));
     if (lora_pending) (void)hipStreamWaitEvent(main_s, v->ev_l, 0);          // the caller's stream owns the gradients again
@@ -437,23 +492,45 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
 }
 
 extern "C" int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream) {
-    CLHIP_CHECK_ARG(v && workspace && out && v->have_last && v->last.save);
-    CLHIP_CHECK_ARG(layer >= 0 && layer <= v->d.depth && which >= 0 && which <= 4 && (layer < v->d.depth || which == 0));
+    CLHIP_CHECK_ARG(v && workspace && out && v->have_last);
+    CLHIP_CHECK_ARG(layer >= 0 && layer <= v->d.depth && which >= 0 && which <= 9 && (layer < v->d.depth || which == 0));
     const Layout& L = v->last;
+    // a forward that did not save keeps one set of buffers for all layers: only the attention inputs of a Gram pass (which 5) are still there
+    CLHIP_CHECK_ARG(L.save || which == 5);
     const size_t D = v->d.dim, M = L.M;
     size_t off, n;
+    int dt = v->dtype;
     switch (which) {
         case 0: off = L.x_in[layer]; n = M * D; break;
         case 1: off = L.qkv[layer]; n = M * 3 * D; break;
         case 2: off = L.attn_o[layer]; n = M * D; break;
         case 3: off = L.x_mid[layer]; n = M * D; break;
-        default: off = L.hpre[layer]; n = M * v->d.mlp; break;
+        case 4: off = L.hpre[layer]; n = M * v->d.mlp; break;
+        case 5:
+            if (!L.h1_own) { clhip_set_error("clhip_vit_read_act: the LN1 output aliases the LN2 scratch in this layout"); return CLHIP_EINVAL; }
+            off = L.h1[layer]; n = M * D; break;
+        case 6: off = L.lse[layer]; n = (size_t)L.B * v->d.heads * L.N; dt = CLHIP_F32; break;
+        case 7: off = L.st1[layer]; n = 2 * M; dt = CLHIP_F32; break;
+        case 8: off = L.st2[layer]; n = 2 * M; dt = CLHIP_F32; break;
+        default:
+            if (v->d.adapter_dim <= 0) { clhip_set_error("clhip_vit_read_act: no adapters in this executor"); return CLHIP_EINVAL; }
+            off = L.ad_hd[layer]; n = M * v->d.adapter_dim; break;
     }
-    const char* src = static_cast<const char*>(workspace) + off;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int blocks = (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
-    if (v->dtype == CLHIP_BF16) hipLaunchKernelGGL(to_f32_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, (const bf16_t*)src, out, n);
-    else hipLaunchKernelGGL(to_f32_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)src, out, n);
-    CLHIP_LAUNCH_CHECK();
+    return vit_to_f32(static_cast<const char*>(workspace) + off, out, n, dt, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int clhip_vit_set_tap(clhip_vit* v, float* buf, size_t floats) {
+    CLHIP_CHECK_ARG(v && (buf != nullptr) == (floats > 0));
+    v->tap = buf; v->tap_cap = floats;
+    return CLHIP_OK;
+}
+
+extern "C" size_t clhip_vit_tap_floats(const clhip_vit* v) {
+    return v && v->have_last && v->last.save ? tap_slot_off(v, v->last, v->d.depth, 0) : 0;
+}
+
+extern "C" int clhip_vit_last_backward_info(const clhip_vit* v, int* side_stream_used, int* lowest_layer_run) {
+    CLHIP_CHECK_ARG(v && side_stream_used && lowest_layer_run && v->info_side >= 0);
+    *side_stream_used = v->info_side; *lowest_layer_run = v->info_lowest;
     return CLHIP_OK;
 }

@@ -719,9 +719,13 @@ class VisionTransformer(nn.Module):
     def debug_read(self, layer, which):
         s = self._s
         B, n_prompt = self._last
-        M = B * (n_prompt + 1 + self.patch_embed.num_patches)
-        width = {0: self.embed_dim, 1: 3 * self.embed_dim, 2: self.embed_dim, 3: self.embed_dim, 4: self.mlp_dim}[which]
-        out = torch.empty(M, width, device=s.ws.device)
+        N = n_prompt + 1 + self.patch_embed.num_patches
+        M = B * N
+        D = self.embed_dim
+        # include/clhip.h, clhip_vit_read_act: 5 the LN1 output, 6 lse [B, H, N], 7 / 8 the LN1 / LN2 statistics [2, M], 9 the adapter's hidden rows
+        shape = {0: (M, D), 1: (M, 3 * D), 2: (M, D), 3: (M, D), 4: (M, self.mlp_dim), 5: (M, D), 6: (B, self.num_heads, N), 7: (2, M), 8: (2, M),
+                 9: (M, self.adapter_dim)}[which]
+        out = torch.empty(*shape, device=s.ws.device)
         call("clhip_vit_read_act", s.handle, s.ws.data_ptr(), layer, which, out.data_ptr(), _st())
         return out
 

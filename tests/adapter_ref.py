@@ -55,6 +55,36 @@ def bwd(gy, x, hd, Wd, Wu, s, p=0.0, q=ident):
     return dh @ q(Wd), dh.T @ x, dh.sum(0), s * gy.T @ hd, s * gy.sum(0), dh
 
 
+# ---- the error bounds of csrc/adapter.hip (tests/test_adapter_kernels_gpu.py states the rule; tests/vit_plan_ref.py applies the same numbers inside the executor)
+U, V16 = 2.0 ** -24, 2.0 ** -8
+
+
+def fwd_bounds(x, y0, Wd, bd, Wu, bu, s, hd64, delta, y64, p, v, q):
+    """(e_hd, e_y): x, y0 = the value y held before the += (fp64), hd64 / delta from `fwd`, y64 = q(y0 + delta); v = V16 in the bf16 mode, else 0"""
+    keep = 1.0 / (1.0 - p) if p > 0 else 1.0
+    D, R = x.shape[1], Wd.shape[0]
+    pre_abs = x.abs() @ q(Wd).abs().T
+    e_hd = keep * (D * U * pre_abs + 2 * U * (pre_abs + bd.abs())) + 2 * v * hd64.abs()
+    e_y = s * (R * U * (hd64.abs() @ q(Wu).abs().T) + e_hd @ q(Wu).abs().T) + 4 * U * (y0.abs() + delta.abs() + s * bu.abs()) + 2 * v * y64.abs()
+    return e_hd, e_y
+
+
+def bwd_bounds(gy, hd64, Wd, Wu, s, dh64, dx64, gx64, p, v, q):
+    """(e_dh, e_gx) of clhip_adapter_bwd"""
+    keep = 1.0 / (1.0 - p) if p > 0 else 1.0
+    D, R = gy.shape[1], Wd.shape[0]
+    t_abs = gy.abs() @ q(Wu).abs()
+    e_dh = (hd64 > 0) * s * keep * (D + 3) * U * t_abs + 2 * v * dh64.abs()
+    e_gx = R * U * (dh64.abs() @ q(Wd).abs()) + e_dh @ q(Wd).abs() + 2 * U * (gy.abs() + dx64.abs()) + 2 * v * gx64.abs()
+    return e_dh, e_gx
+
+
+def wgrad_bounds(gy, hd64, x, dh64, s):
+    """bounds of (dWd, dbd, dWu, dbu) of clhip_adapter_wgrad: fp32 accumulation over the M rows of stored tensors, nothing else"""
+    MU = (gy.shape[0] + 2) * U
+    return MU * (dh64.abs().T @ x.abs()), MU * dh64.abs().sum(0), s * MU * (gy.abs().T @ hd64.abs()), s * MU * gy.abs().sum(0)
+
+
 def autograd(gy, x, Wd, bd, Wu, bu, s, mask=None, p=0.0):
     """the same gradients from torch autograd of the plain formula (no rounding)"""
     leaves = [t.detach().clone().requires_grad_(True) for t in (x, Wd, bd, Wu, bu)]

@@ -58,6 +58,38 @@ def grads(X, dqkv, Aq, Bq, Av, Bv, mag, inv_q, inv_v):
     return out[0], out[1], out[2], out[3], dm
 
 
+def grads_bounded(X64, dY64, host, mag, inv, q, v):
+    """clhip_sdlora_grad's five results with their error bounds (the rule and the numbers of tests/test_sdlora_kernels_gpu.py, which imports this; the
+    executor's test applies the same).  host = [A_q terms, B_q terms, A_v terms, B_v terms] (fp32 masters), mag [T + 1], inv [2, T + 1]; q rounds a factor to the
+    compute dtype where the MFMA products read it, v = 2^-8 in the bf16 mode, else 0.  -> ([dA_q, dB_q, dA_v, dB_v, dmag], the same five bounds)"""
+    U = 2.0 ** -24
+    M, D = X64.shape
+    m64, inv64, T1 = mag.double(), inv.double(), len(host[0])
+    mT = m64[-1]
+    want_dm, e_dm = torch.zeros(T1, dtype=torch.float64), torch.zeros(T1, dtype=torch.float64)
+    want, bound = [None] * 5, [None] * 5
+    for w, dYw in ((0, dY64[:, :D]), (1, dY64[:, 2 * D:])):
+        A, B = host[2 * w], host[2 * w + 1]
+        for i in range(T1):
+            A16, Bi = q(A[i]).double(), B[i].double()
+            P = X64 @ A16.T
+            eP = D * U * (X64.abs() @ A16.abs().T) + 2 * v * P.abs()
+            S = dYw.T @ P
+            eS = dYw.abs().T @ eP + (M + 2) * U * (dYw.abs().T @ P.abs())
+            term = inv64[w, i] * (S * Bi).sum()
+            want_dm[i] += term
+            e_dm[i] += inv64[w, i].abs() * ((eS * Bi.abs()).sum() + (D * A[i].shape[0] + 3) * U * (S.abs() * Bi.abs()).sum()) + 2 * U * term.abs()
+        want[2 * w + 1] = mT * S                                                                       # (S of the last term)
+        bound[2 * w + 1] = mT.abs() * eS + U * want[2 * w + 1].abs()
+        B16 = q(B[-1]).double()
+        Uw = dYw @ B16
+        eU = D * U * (dYw.abs() @ B16.abs()) + 2 * v * Uw.abs()
+        want[2 * w] = mT * (Uw.T @ X64)
+        bound[2 * w] = mT.abs() * (eU.T @ X64.abs() + (M + 2) * U * (Uw.abs().T @ X64.abs())) + U * want[2 * w].abs()
+    want[4], bound[4] = want_dm, e_dm + U * want_dm.abs()
+    return want, bound
+
+
 # ------------------------------------------------------------------------------------------------- the method on the tiny ViT
 class Method:
     """SD_LoRA on a dict of fp64 tensors: the state `before_task` leaves is loaded from the fixture (its random draws are the reference's)"""

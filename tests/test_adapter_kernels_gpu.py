@@ -87,14 +87,11 @@ def _check_all(M, D, R, dtype, p, seed_t=None, layer=0):
     dev, ref, W, W64 = _inputs(M, D, R, dtype, seed=layer)
     Wd, bd, Wu, bu = W64
     mask = _mask(seed_t, layer, M, R, p).cpu() if p > 0 else None
-    keep = 1.0 / (1.0 - p) if p > 0 else 1.0
     # ---- forward
     y, hd = _fwd(dev, W, dtype, p, seed_t, layer)
     delta, hd64 = A.fwd(ref["x"], Wd, bd, Wu, bu, S, mask, p, q)
     y64 = q(ref["y"] + delta)
-    pre_abs = ref["x"].abs() @ q(Wd).abs().T
-    e_hd = keep * (D * U * pre_abs + 2 * U * (pre_abs + bd.abs())) + 2 * v * hd64.abs()
-    e_y = S * (R * U * (hd64.abs() @ q(Wu).abs().T) + e_hd @ q(Wu).abs().T) + 4 * U * (ref["y"].abs() + delta.abs() + S * bu.abs()) + 2 * v * y64.abs()
+    e_hd, e_y = A.fwd_bounds(ref["x"], ref["y"], Wd, bd, Wu, bu, S, hd64, delta, y64, p, v, q)      # (the numbers live in adapter_ref: the executor's test shares them)
     r_fwd = max(_ratio(hd, hd64, e_hd), _ratio(y, y64, e_y))
     assert float((y.double().cpu() - ref["y"]).abs().max()) > 0                       # the branch did add something
     # ---- input gradient, on the restatement's own hd (the kernels are tested alone)
@@ -102,17 +99,14 @@ def _check_all(M, D, R, dtype, p, seed_t=None, layer=0):
     dh, gx = _bwd(dev["gy"], hd_dev, W, dtype, p)
     dx64, dWd64, dbd64, dWu64, dbu64, dh64 = A.bwd(ref["gy"], ref["x"], hd64, Wd, Wu, S, p, q)
     gx64 = q(ref["gy"] + dx64)
-    t_abs = ref["gy"].abs() @ q(Wu).abs()
-    e_dh = (hd64 > 0) * S * keep * (D + 3) * U * t_abs + 2 * v * dh64.abs()
-    e_gx = R * U * (dh64.abs() @ q(Wd).abs()) + e_dh @ q(Wd).abs() + 2 * U * (ref["gy"].abs() + dx64.abs()) + 2 * v * gx64.abs()
+    e_dh, e_gx = A.bwd_bounds(ref["gy"], hd64, Wd, Wu, S, dh64, dx64, gx64, p, v, q)
     r_bwd = max(_ratio(dh, dh64, e_dh), _ratio(gx, gx64, e_gx))
     dh2, gx2 = _bwd(dev["gy"], hd_dev, W, dtype, p, in_place=True)                    # gx may be gy
     assert torch.equal(dh2, dh) and torch.equal(gx2, gx)
     # ---- parameter gradients, on stored tensors only: fp32 accumulation over M rows, nothing else
     dh_dev = dh64.to(DT[dtype][1]).to(DEV)
     got = _wgrad(dev["gy"], hd_dev, dev["x"], dh_dev, dtype)
-    MU = (M + 2) * U
-    bounds = (MU * (dh64.abs().T @ ref["x"].abs()), MU * dh64.abs().sum(0), S * MU * (ref["gy"].abs().T @ hd64.abs()), S * MU * ref["gy"].abs().sum(0))
+    bounds = A.wgrad_bounds(ref["gy"], hd64, ref["x"], dh64, S)
     r_wg = max(_ratio(a, b, c) for a, b, c in zip(got, (dWd64, dbd64, dWu64, dbu64), bounds))
     print(f"adapter M={M} D={D} R={R} {dtype} p={p}: largest error / bound  fwd {r_fwd:.3f}  bwd {r_bwd:.3f}  wgrad {r_wg:.3f}")
     assert r_fwd <= 1.0 and r_bwd <= 1.0 and r_wg <= 1.0

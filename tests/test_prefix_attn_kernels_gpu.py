@@ -56,29 +56,8 @@ def launch(qkv, pk, pv, dout, B, N, Lp, H, hd, dt):
 
 
 def references(big, bd, B, N, Lp, H, hd, dt):
-    """fp64 reference of the packed form cut to the rows the prefix kernels produce: {tensor: (ref, relative bound, elementwise extra)} for out, dq, dk, dv
-    (token rows) and dpk, dpv (prefix rows), the conditioning of the token queries' exponent [B,H,N], and the whole lse reference [B,H,T]"""
-    T = N + Lp
-    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = V.attn_ref(big, bd, B, T, H, hd)
-    assert float(ref_dq[:, :, :Lp].abs().max()) == 0.0                       # zero dout: the prefix rows' queries get nothing, as the kernel assumes
-    labs = V.attn_logit_abs(big, B, T, H, hd)[:, :, Lp:]                     # [B,H,N]: the token queries
-    cond = hd * U * labs
-    bf = dt == "bf16"
-    mfma = bf and hd == 64
-    cq, ck = V.attn_cancel_bound(big, bd, B, T, H, hd, 2.0 ** -9 if bf else U, 2.0 ** -9 if mfma else T * U)
-
-    def amax(t):
-        return t.abs().amax(dim=(-1, -2), keepdim=True)
-    tok, pre = (lambda t: t[:, :, Lp:]), (lambda t: t[:, :, :Lp])
-    cmax = cond.amax(-1)[..., None, None]
-    store = 2.0 ** -9 if bf else 0.0                                          # the bf16 store step dpk / dpv do not have
-    bounds = {"out": (tok(ref_o), V.ATTN_OUT[dt], cond[..., None] * amax(tok(ref_o)).expand_as(tok(ref_o))),
-              "dq": (tok(ref_dq), V.ATTN_GRAD[dt], tok(cq) + cond[..., None] * amax(tok(ref_dq))),
-              "dk": (tok(ref_dk), V.ATTN_GRAD[dt], tok(ck) + cmax * amax(tok(ref_dk))),
-              "dv": (tok(ref_dv), V.ATTN_GRAD[dt], (cmax * amax(tok(ref_dv))).expand_as(tok(ref_dv))),
-              "dpk": (pre(ref_dk), V.ATTN_GRAD[dt] - store, pre(ck) + cmax * amax(pre(ref_dk))),
-              "dpv": (pre(ref_dv), V.ATTN_GRAD[dt] - store, (cmax * amax(pre(ref_dv))).expand_as(pre(ref_dv)))}
-    return bounds, cond, ref_lse
+    """vit_refs.attn_references (the numbers live there: the executor's test shares them)"""
+    return V.attn_references(big, bd, B, N, Lp, H, hd, dt)
 
 
 def run_prefix(big, bd, B, N, Lp, H, hd, dt, tag):

@@ -137,6 +137,41 @@ def attn_cancel_bound(qkv, dout, B, N, H, hd, eps_o, eps_ds):
     return scale * (ds_err @ k.abs()), scale * (ds_err.transpose(-2, -1) @ q.abs())
 
 
+def attn_references(big, bd, B, N, Lp, H, hd, dt):
+    """fp64 reference of the packed form (coda_ref.pack_prefix; Lp = 0: plain attention) cut to the rows the kernels produce: {tensor: (ref, relative
+    bound, elementwise extra)} for out, dq, dk, dv (token rows) and dpk, dpv (prefix rows), the conditioning of the token queries' exponent [B,H,N], and the
+    whole lse reference [B,H,T].  The bounds of run_attention (tests/test_vit_ops_kernels_gpu.py) / run_prefix (tests/test_prefix_attn_kernels_gpu.py), which
+    the executor's test shares: judged per (batch, head) block by `blocked_ratio`"""
+    T = N + Lp
+    ref_o, ref_lse, ref_dq, ref_dk, ref_dv = attn_ref(big, bd, B, T, H, hd)
+    assert float(ref_dq[:, :, :Lp].abs().max()) == 0.0 if Lp else True       # zero dout: the prefix rows' queries get nothing, as the kernel assumes
+    labs = attn_logit_abs(big, B, T, H, hd)[:, :, Lp:]                       # [B,H,N]: the token queries
+    cond = hd * U * labs
+    bf = dt == "bf16"
+    mfma = bf and hd == 64
+    cq, ck = attn_cancel_bound(big, bd, B, T, H, hd, 2.0 ** -9 if bf else U, 2.0 ** -9 if mfma else T * U)
+
+    def amax(t):
+        return t.abs().amax(dim=(-1, -2), keepdim=True)
+    tok, pre = (lambda t: t[:, :, Lp:]), (lambda t: t[:, :, :Lp])
+    cmax = cond.amax(-1)[..., None, None]
+    store = 2.0 ** -9 if bf else 0.0                                          # the bf16 store step dpk / dpv do not have
+    bounds = {"out": (tok(ref_o), ATTN_OUT[dt], cond[..., None] * amax(tok(ref_o)).expand_as(tok(ref_o))),
+              "dq": (tok(ref_dq), ATTN_GRAD[dt], tok(cq) + cond[..., None] * amax(tok(ref_dq))),
+              "dk": (tok(ref_dk), ATTN_GRAD[dt], tok(ck) + cmax * amax(tok(ref_dk))),
+              "dv": (tok(ref_dv), ATTN_GRAD[dt], (cmax * amax(tok(ref_dv))).expand_as(tok(ref_dv)))}
+    if Lp:
+        bounds["dpk"] = (pre(ref_dk), ATTN_GRAD[dt] - store, pre(ck) + cmax * amax(pre(ref_dk)))
+        bounds["dpv"] = (pre(ref_dv), ATTN_GRAD[dt] - store, (cmax * amax(pre(ref_dv))).expand_as(pre(ref_dv)))
+    return bounds, cond, ref_lse
+
+
+def blocked_allowed(ref, rel, extra=None):
+    """the elementwise bound of a [B,H,...] tensor judged per (batch, head) block: rel * the block's max|ref| + 1e-7 max|ref| of the tensor, or `extra` where larger"""
+    allowed = rel * ref.abs().amax(dim=(-1, -2), keepdim=True).expand_as(ref) + FLOOR * float(ref.abs().max())
+    return allowed if extra is None else larger(allowed, extra)
+
+
 def attn_inputs(B, N, H, hd, seed, dt):
     """the inputs of the existing attention test: qkv = 1.5 randn, dout = randn, rounded to the mode's dtype"""
     D = H * hd
