@@ -6,6 +6,8 @@
  *   core/trainer.py:585-612            (the batch loop)
  *   core/model/{finetune,ewc,lwf,icarl,lucir}.py  (observe / inference / Fisher)
  *   core/model/backbone/resnet.py      (ResNet forward)
+ *   core/model/backbone/{transformer,vit,prompt}.py  (the frozen ViT, its prompted forward and the prompt pools
+ *                                       of L2P, CODA-Prompt and DualPrompt: clhip_vit_*, clhip_l2p_*, clhip_coda_*, clhip_dual_*)
  * The entry points below are what those call sites bind to in the drop-in (INTEGRATION.md shows
  * the ctypes stubs); each declaration cites the reference lines whose arithmetic it replaces.
  *
@@ -638,6 +640,23 @@ int clhip_coda_fwd(int layers, const float* q, const float* const* K, const floa
 int clhip_coda_bwd(int layers, const float* q, const float* const* K, const float* const* A, const float* const* P, const float* c, const float* const* dpk,
                    const float* const* dpv, float* const* dK, float* const* dA, float* const* dP, float* ws, int B, int D, int pool, int L, int s, int f,
                    void* stream);
+/* DualPrompt's prompt selection, DualPrompt.forward (prompt.py:269-337) for n_g G-layers and n_e E-layers in one launch, exact fp32.  g_p, e_k, e_p, dg_p,
+ * de_k, de_p: HOST arrays of n_g / n_e device pointers; pk, pv, dpk, dpv: HOST arrays of n_g + n_e device pointers, the G-layers first.  Per G-layer
+ * g_p [Lg, D]; per E-layer e_k [pool, D], e_p [pool, Le, D] (fp32 masters); q [B, D] fp32 (shared by the layers).
+ * fwd: G-layer (prompt.py:310-316): pk[b] = g_p[:Lg/2], pv[b] = g_p[Lg/2:] for every sample.
+ *      E-layer: cos[l,b,k] = <q_b, K_k> / (max(|q_b|, 1e-12) max(|K_k|, 1e-12)) for all k < pool (prompt.py:279-281), kept as cos [n_e, B, pool] fp32;
+ *      idx[l,b] (int32, [n_e, B]) = task_id when `train` (prompt.py:285-287), else the arg-max of cos[l,b,:], an exact tie going to the lowest index
+ *      (prompt.py:294-296, top-1); pk[b] = e_p[idx][:Le/2], pv[b] = e_p[idx][Le/2:] (prompt.py:299-306).  pk, pv [B, L/2, D] in the compute dtype: the
+ *      pk / pv of clhip_attn_prefix_fwd; a copy (bf16: one rounding).
+ *      train: loss[0] = sum over the E-layers in order of sum_b (1 - cos[l,b,task_id]), b in order (prompt.py:286, transformer.py:2279); eval: not written.
+ * bwd: from dpk, dpv [B, L/2, D] fp32 writes dg_p = sum_b [dpk_b | dpv_b] ([Lg, D]), row task_id of de_p [pool, Le, D] by the same sum, and row task_id of
+ *      de_k [pool, D] = dloss[0] * d(key loss)/d e_k (dloss: one fp32 on the device) -- and nothing outside them; q gets no gradient; the batch is summed
+ *      in order (bit-reproducible).
+ * D % 64 == 0, Lg / Le even and >= 2, 0 <= task_id < pool (fwd: in train mode), n_g, n_e <= 8 and not both 0. */
+int clhip_dual_fwd(int n_g, int n_e, const float* q, const float* const* g_p, const float* const* e_k, const float* const* e_p, void* const* pk, void* const* pv,
+                   float* cos, int* idx, float* loss, int B, int D, int pool, int Lg, int Le, int train, int task_id, int dtype, void* stream);
+int clhip_dual_bwd(int n_g, int n_e, const float* q, const float* const* e_k, const float* const* dpk, const float* const* dpv, const float* dloss,
+                   float* const* dg_p, float* const* de_k, float* const* de_p, int B, int D, int pool, int Lg, int Le, int task_id, void* stream);
 /* nn.LayerNorm over the last dim (transformer.py:1331-1336): y = (x-mean)*rstd*gamma+beta; mean/rstd [M] saved when given */
 int clhip_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps,
                  int dtype, void* stream);

@@ -180,6 +180,8 @@ _PROTOS = {
     "clhip_coda_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "clhip_coda_fwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "clhip_coda_bwd": (_i, [_i] + [_p] * 11 + [_i] * 6 + [_p]),
+    "clhip_dual_fwd": (_i, [_i, _i] + [_p] * 9 + [_i] * 8 + [_p]),
+    "clhip_dual_bwd": (_i, [_i, _i] + [_p] * 8 + [_i] * 6 + [_p]),
     "clhip_ln_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p]),
     "clhip_ln_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "clhip_ln_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),

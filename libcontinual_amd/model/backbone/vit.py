@@ -11,6 +11,7 @@ kwargs and plugin code written against it keep working:
     MultiHeadAttention_SDLoRA  transformer.py:276-357   (lora_{A,B}_{q,v}_list, mag_lora, assimilated_mag_lora_{q,v}, init_param)
     L2PPrompt                  core/model/backbone/prompt.py:345-406 (prompt, prompt_key)
     CodaPromptPool             core/model/backbone/prompt.py:37-223  (e_p_{l}, e_k_{l}, e_a_{l}, task_count, process_task_count, gram_schmidt)
+    DualPromptPool             core/model/backbone/prompt.py:231-337 (g_p_{l}, e_p_{l}, e_k_{l}, task_count, process_task_count)
 
 The modules below only OWN parameters (fp32 masters on the device); they have no forward of their own.  All
 compute happens in `VisionTransformer.features()`: ONE C call for the whole forward and ONE for the whole backward
@@ -341,6 +342,61 @@ class _CodaFn(torch.autograd.Function):
         return (None,) * 8 + tuple(grads)
 
 
+class _DualFn(torch.autograd.Function):
+    """query pass (no prefix) -> prompt selection (clhip_dual_fwd) -> prefixed forward; backward = clhip_vit_backward_prefix -> clhip_dual_bwd.
+    -> (features, key loss [1]).  `params` = g_p of every G-layer, then e_k, e_p of every E-layer, in layer order"""
+
+    @staticmethod
+    def forward(ctx, vit, pool, images, need, train, task_id, *params):
+        q = vit._run_forward(images, None, 0, None)                      # norm(x)[:, 0] of the prompt-free forward (vit.py:121-123)
+        gl, el, Lg, Le, size = pool.g_layers, pool.e_layers, pool.g_p_length, pool.e_p_length, pool.e_pool_size
+        B, D, ng, ne = q.shape[0], vit.embed_dim, len(gl), len(el)
+        dev, (code, tdt) = q.device, _DT[vit.compute_dtype]
+        for t in params:
+            require_gpu(t)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.ClhipError("the DualPrompt pool must be contiguous fp32")
+        g_p, e_k, e_p = params[:ng], params[ng::2], params[ng + 1::2]
+        pre = [torch.empty(2, B, L // 2, D, device=dev, dtype=tdt) for L in [Lg] * ng + [Le] * ne]
+        cos = torch.empty(ne, B, size, device=dev)
+        idx = torch.empty(ne, B, device=dev, dtype=torch.int32)
+        loss = torch.zeros(1, device=dev)                                # (eval mode leaves it alone)
+        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        call("clhip_dual_fwd", ng, ne, q.data_ptr(), arr(g_p), arr(e_k), arr(e_p), arr([p[0] for p in pre]), arr([p[1] for p in pre]), cos.data_ptr(),
+             idx.data_ptr(), loss.data_ptr(), B, D, size, Lg, Le, int(train), int(task_id) if train else 0, code, _st())
+        lp, pk, pv = [0] * vit.depth, [None] * vit.depth, [None] * vit.depth
+        for i, l in enumerate(list(gl) + list(el)):
+            lp[l], pk[l], pv[l] = pre[i].shape[2], pre[i][0], pre[i][1]
+        feat = vit._run_forward(images, None, need, None, prefix=(lp, pk, pv))
+        pool.last_cos, pool.last_idx = cos, idx
+        ctx.vit, ctx.token, ctx.lp, ctx.pool, ctx.task_id, ctx.train = vit, vit._fwd_token, lp, pool, task_id, train
+        ctx.keep = (q, pre)                                              # pre: the executor reads the prefixes again in the backward
+        ctx.params = params
+        return feat, loss
+
+    @staticmethod
+    def backward(ctx, dfeat, dloss):
+        vit, pool = ctx.vit, ctx.pool
+        if vit._fwd_token != ctx.token:
+            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        if not ctx.train:
+            raise RuntimeError("DualPrompt: the inference selection (arg-max over the keys) has no backward")
+        q, _ = ctx.keep
+        gl, el = pool.g_layers, pool.e_layers
+        B, D, ng, ne = q.shape[0], vit.embed_dim, len(gl), len(el)
+        if dfeat is None:
+            dfeat = torch.zeros(B, D, device=q.device)
+        dloss = torch.zeros(1, device=q.device) if dloss is None else dloss.float().reshape(1).contiguous()
+        dpk, dpv = vit._run_backward_prefix(dfeat, ctx.lp)
+        params = ctx.params
+        grads = [torch.zeros_like(t) for t in params]                    # rows other than task_id get no gradient
+        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        order = list(gl) + list(el)
+        call("clhip_dual_bwd", ng, ne, q.data_ptr(), arr(params[ng::2]), arr([dpk[l] for l in order]), arr([dpv[l] for l in order]), dloss.data_ptr(),
+             arr(grads[:ng]), arr(grads[ng::2]), arr(grads[ng + 1::2]), B, D, pool.e_pool_size, pool.g_p_length, pool.e_p_length, int(ctx.task_id), _st())
+        return (None,) * 6 + tuple(grads)
+
+
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, attn_layer="MultiHeadAttention",
                  mlp_ratio=4.0, dtype="bf16", lora_rank=0, ffn_adapt=False, ffn_num=64, ffn_adapter_scalar=0.1, adapter_dropout=0.1, **kwargs):
@@ -651,6 +707,20 @@ class VisionTransformer(nn.Module):
         s_, f_ = pool.window()
         return _CodaFn.apply(self, tuple(pool.e_layers), images, need, s_, f_, pool.e_pool_size, pool.e_p_length, *params)
 
+    def dual_features(self, images, pool, train=False, task_id=None):
+        """ViTZoo.forward with a DualPrompt pool (vit.py:120-127) -> (features [B, D] fp32, key loss [1]): the final-LN output at the cls token of the
+        forward whose blocks `pool.g_layers` attend over the shared G-prompts and whose blocks `pool.e_layers` attend over one E-prompt per sample -- row
+        `task_id` when `train` (with the key loss of prompt.py:286), else the row whose key is closest to the query (key loss 0).  Differentiable in
+        train mode w.r.t. the G-prompts and row `task_id` of the E-prompts and keys.  `pool.last_cos` [E-layers, B, pool] and `pool.last_idx` keep the
+        cosines and the selection of the last call."""
+        if self.lora_rank or self.sd_lora or self.adapter_dim:
+            raise NotImplementedError("DualPrompt runs on the plain frozen backbone")
+        if train and (task_id is None or not 0 <= int(task_id) < pool.e_pool_size):
+            raise ValueError(f"DualPrompt: training indexes the pool by task_id, got {task_id} for a pool of {pool.e_pool_size} (prompt.py:287)")
+        params = pool.layer_tensors()
+        need = bool(train) and torch.is_grad_enabled() and any(t.requires_grad for t in params)
+        return _DualFn.apply(self, pool, images, need, bool(train), task_id, *params)
+
     # --------------------------------------------------------------------------------------- public forward
     def _gram_buffer(self, dev):
         """the resident [depth, D, D] fp32 sums of X^T X; layer i's LazyGram (if its attention module has one) owns row i"""
@@ -713,7 +783,7 @@ class VisionTransformer(nn.Module):
             tokens, reduce_sim = prompt(None, cls_features=cls_features)
             return self.features(x, tokens), reduce_sim
         if prompt is not None:
-            raise NotImplementedError("prefix prompting goes through coda_features (ViTZoo.forward); DualPrompt is outside the hot-path scope")
+            raise NotImplementedError("prefix prompting goes through coda_features / dual_features (ViTZoo.forward)")
         return self.features(x, None, get_input_matrix), None
 
     def debug_read(self, layer, which):
@@ -870,6 +940,42 @@ class CodaPromptPool(nn.Module):
         return nn.Parameter(uu.T.reshape(shape).contiguous())
 
 
+class DualPromptPool(nn.Module):
+    """prompt.DualPrompt (prompt.py:231-337): the shared G-prompts g_p_{l} [Lg, D] of the blocks `g_layers` and, per block l in `e_layers`, a pool of E-prompts
+    e_p_{l} [pool, Le, D] with their keys e_k_{l} [pool, key_dim].  prompt_param = [pool, Le, Lg] (prompt.py:262-264).  Construction makes the reference's
+    draws from torch's CPU generator in its order (prompt.py:241-251: uniform_ for g_p_0, g_p_1, then per E-layer p, k), so a seeded run starts from the
+    reference's tensors bit for bit.  Training indexes the pool by task id (`task_id_bootstrap`, prompt.py:255, is hard-coded True and the branch for False
+    is not built).  The module only owns the parameters: VisionTransformer.dual_features selects the prefixes (csrc/dual.hip) and runs the blocks."""
+
+    def __init__(self, emb_d, n_tasks, prompt_param, key_dim=768):
+        super().__init__()
+        self.task_count, self.emb_d, self.key_d, self.n_tasks = 0, emb_d, key_dim, n_tasks
+        self.top_k, self.task_id_bootstrap = 1, True
+        self.g_layers, self.e_layers = [0, 1], [2, 3, 4]
+        self.e_pool_size, self.e_p_length, self.g_p_length = int(prompt_param[0]), int(prompt_param[1]), int(prompt_param[2])
+        if key_dim != emb_d:
+            raise NotImplementedError("the query is the backbone's cls feature: key_dim must equal the embedding width (prompt.py:281 contracts them)")
+        for name, n in (("e_prompt_length", self.e_p_length), ("g_prompt_length", self.g_p_length)):
+            if n % 2 or n < 2:
+                raise NotImplementedError(f"{name} must be even: rows [:n/2] are the key prefix and rows [n/2:] the value prefix (prompt.py:300-302, "
+                                          ":312-316), which the attention concatenates to keys and values of one length (transformer.py:175-180)")
+        if n_tasks > self.e_pool_size:
+            raise NotImplementedError(f"task_num {n_tasks} > pool size {self.e_pool_size}: training takes row task_id of the pool (prompt.py:287)")
+        for g in self.g_layers:
+            setattr(self, f"g_p_{g}", nn.Parameter(nn.init.uniform_(torch.empty(self.g_p_length, emb_d, dtype=torch.float32))))
+        for e in self.e_layers:
+            setattr(self, f"e_p_{e}", nn.Parameter(nn.init.uniform_(torch.empty(self.e_pool_size, self.e_p_length, emb_d, dtype=torch.float32))))
+            setattr(self, f"e_k_{e}", nn.Parameter(nn.init.uniform_(torch.empty(self.e_pool_size, self.key_d, dtype=torch.float32))))
+        self.last_cos = self.last_idx = None
+
+    def process_task_count(self):
+        self.task_count += 1
+
+    def layer_tensors(self):
+        """g_p of every G-layer, then e_k, e_p of every E-layer, in layer order"""
+        return [getattr(self, f"g_p_{g}") for g in self.g_layers] + [getattr(self, f"e_{w}_{e}") for e in self.e_layers for w in ("k", "p")]
+
+
 class ViTZoo(nn.Module):
     """core/model/backbone/vit.py:43-139.  Extra kwargs (img_size, patch_size, embed_dim, depth, num_heads, dtype) size
     the model for tests; the defaults are the reference's hard-coded ViT-B/16."""
@@ -915,8 +1021,11 @@ class ViTZoo(nn.Module):
         elif prompt_flag == "coda":
             kwargs.setdefault("key_dim", self.feat_dim)                    # (vit.py:97 hard-codes 768 for both; here the backbone's width)
             self.prompt = CodaPromptPool(self.feat_dim, **kwargs)
+        elif prompt_flag == "dual":
+            kwargs.setdefault("key_dim", self.feat_dim)                    # (vit.py:95 likewise)
+            self.prompt = DualPromptPool(self.feat_dim, **kwargs)
         else:
-            raise NotImplementedError("only the L2P and CODA-Prompt pools are on the hot path (SURVEY.md section 8)")
+            raise NotImplementedError("only the L2P, DualPrompt and CODA-Prompt pools are on the hot path (SURVEY.md section 8)")
         self.prompt_flag = prompt_flag
 
     def forward(self, image, text=None, pen=False, train=False, **kwargs):
@@ -928,6 +1037,10 @@ class ViTZoo(nn.Module):
             # vit.py:120-138: query pass without gradient, prompted pass, the cls feature; the prompt loss is the orthogonality penalty, 0 at mu = 0
             out = self.feat.coda_features(image, self.prompt, train=train)
             return (out, torch.zeros(1, device=out.device)) if train else out
+        if self.prompt_flag == "dual":
+            # the same lines with a DualPrompt pool: the prompt loss is the key loss of the three E-layers, shape (1,) (transformer.py:2272-2279)
+            out, prompt_loss = self.feat.dual_features(image, self.prompt, train=train, task_id=self.task_id)
+            return (out, prompt_loss) if train else out
         if self.prompt is not None:
             raise NotImplementedError
         out, _ = self.feat(image, **kwargs)
