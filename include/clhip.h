@@ -746,6 +746,36 @@ int clhip_sdlora_grad(const void* x, const void* dqkv, const float* const* facto
                       float* d_a_q, float* d_b_q, float* d_a_v, float* d_b_v, float* d_mag_row, void* ws, int M, int D, int dtype, void* stream);
 int clhip_sdlora_mag_reduce(const float* rows, int depth, int nterms, float* d_mag, void* stream);
 
+/* LoRA-Sub-DRS (core/model/lora_sub.py; MultiHeadAttention_LoRA_Sub, core/model/backbone/transformer.py:359-444; csrc/lorasub.hip).  Exact fp32, no atomics,
+ * every sum in a fixed order: two runs are bitwise equal.  Every call refuses bad arguments before it launches anything.
+ * atl     : AugmentedTripletLoss.forward (lora_sub.py:34-68, the Python double loop over batch x prototypes at :51-63) and its autograd backward in two
+ *           launches.  f [B, D] the UN-normalised features, labels [B], protos [P, D] un-normalised (NULL iff P == 0).  With n_i = f_i / |f_i| and
+ *           c_p = proto_p / |proto_p|:  d_ij = sqrt(max(|n_i - n_j|^2, 1e-12)), e_ip = max(|n_i - c_p|, 1e-12), both summed from the DIFFERENCES (the
+ *           expansion |a|^2 + |b|^2 - 2ab of :41-43 loses the self and near pairs in fp32);  ap_i = max over {j: y_j == y_i} (j = i included),
+ *           an_i = min over {j: y_j != y_i}, or ap_i + margin when there is none, then the smallest e_ip if it is < an_i;  ties go to the lower index,
+ *           batch rows before prototypes.  loss[0] = mean_i max(0, ap_i - an_i + margin) (unweighted; a row without any negative counts 0),
+ *           df [B, D] = weight * d loss / d f, WRITTEN: through both ends of a selected batch pair (row j gathers, in ascending i, the rows that
+ *           selected it), the n_i end of a prototype pair, nothing through a clamped distance, and through the normalisation as (g - n (n.g)) / |f|.
+ *           1 <= B <= 256, 0 <= P <= 1024, D % 64 == 0 and D <= 8192 (one normalised row in LDS).  ws: clhip_atl_ws_bytes(B, P) bytes.
+ * lora_grad_ab: replaces autograd through transformer.py:401-424 for one layer when A and B both train: X [M, D] the attention input, dK / dV the k / v
+ *           column blocks of dqkv [M, 3D] (compute dtype), the factors fp32 (A [r, D], B [D, r]):  d_b = dK^T (X A^T) [D, r], d_a = (dK B)^T X [r, D], the
+ *           same for v.  All four WRITTEN.  The K = D products run on clhip_gemm_nt, the K = M products are slab partials (csrc/tn_slab.hip) reduced in slab
+ *           order.  Rank 1..16, any M >= 1, D % 64 == 0.  ws: clhip_lora_grad_ab_ws_bytes(M, D) bytes.
+ * proj_adam_multi: the projected Adam step of lora_sub.py:120-157, :193-233 over `count` = 4 * layers factor tensors in at most two launches.  tensors:
+ *           DEVICE table [count][4] of pointers (p, g, m, v), per layer in the order A_k [r, D], B_k [D, r], A_v, B_v;  transforms: DEVICE table [layers] of
+ *           T_l [D, D] fp32, or NULL = plain Adam (task 0: one launch, element for element clhip_adam_step with grad_scale 1).  Moments and bias
+ *           correction as clhip_adam_step (weight_decay joins the gradient first); with q = m / (sqrt(v) / sqrt(bc2) + eps), the scalar step factored out
+ *           of the product:  B <- B - (lr / bc1) (T_l q),  A <- A - (lr / bc1) (q T_l), each element accumulated in ascending index.  T_l is read once
+ *           for the two B and once for the two A of a layer.  Rank 1..16, D % 32 == 0.  ws: count * D * rank floats. */
+size_t clhip_atl_ws_bytes(int B, int P);
+int clhip_atl(const float* f, const int64_t* labels, const float* protos /*nullable*/, int B, int D, int P, float margin, float weight, float* loss,
+              float* df, void* ws, void* stream);
+size_t clhip_lora_grad_ab_ws_bytes(int M, int D);
+int clhip_lora_grad_ab(const void* x, const void* dqkv, const float* lora_a_k, const float* lora_b_k, const float* lora_a_v, const float* lora_b_v,
+                       float* d_a_k, float* d_b_k, float* d_a_v, float* d_b_v, void* ws, int M, int D, int rank, int dtype, void* stream);
+int clhip_proj_adam_multi(int count, void* const* tensors, const float* const* transforms /*nullable*/, float* ws, int D, int rank, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
+
 /* Whole-backbone executor: one C call per forward / backward (VisionTransformer.forward, transformer.py:2222-2294, and
  * the autograd backward of L2P.observe / the trainer's loss.backward()). */
 typedef struct clhip_vit_desc {
@@ -799,6 +829,15 @@ int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, const float
 int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream);
 int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
                               float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream);
+/* LoRA-Sub-DRS: A and B of the k / v LoRA terms both train (lora_rank > 0; the layers' qkv_w point at the caller's composed fp32 masters).
+ * lora_refresh_ab: the per-step refresh when A moves too -- the k / v rows of all layers' qkv copies (W + B A, one launch); the q rows and every other weight
+ *   copy keep the rounding of the last clhip_vit_prep_weights.  The [A_k; A_v] operand of clhip_lora_grad is NOT refreshed: clhip_vit_backward's d_lora_b is
+ *   for a fixed A (InfLoRA) and must not follow this call without a full clhip_vit_prep_weights.
+ * backward_lora_ab: clhip_vit_backward that runs clhip_lora_grad_ab per layer: d_factors = [4 * depth] pointers (d A_k, d B_k, d A_v, d B_v of the layer, all
+ *   written); ab_ws: clhip_lora_grad_ab_ws_bytes(M, D) bytes of the caller's, M = B * tokens of the saved forward. */
+int clhip_vit_lora_refresh_ab(clhip_vit*, const clhip_vit_params* params, void* shadow, void* stream);
+int clhip_vit_backward_lora_ab(clhip_vit*, const clhip_vit_params* params, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                               float* const* d_factors, void* ab_ws, void* stream);
 /* Prefix mode of the executor (VisionTransformer.forward with `prompt`, transformer.py:2272-2288: blocks whose prompt is not None attend over
  * [prefix | tokens]).  New entry points; descriptors and parameter tables are untouched.
  * set_prefix: Lp [depth] (host, copied; 0 = a plain layer, at least one > 0), pk / pv [depth] host arrays of device pointers to [B, Lp[l], D] in the

@@ -220,9 +220,16 @@ _PROTOS = {
     "clhip_sdlora_grad_ws_bytes": (_sz, [_i, _i, _i]),
     "clhip_sdlora_grad": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "clhip_sdlora_mag_reduce": (_i, [_p, _i, _i, _p, _p]),
+    "clhip_atl_ws_bytes": (_sz, [_i, _i]),
+    "clhip_atl": (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
+    "clhip_lora_grad_ab_ws_bytes": (_sz, [_i, _i]),
+    "clhip_lora_grad_ab": (_i, [_p] * 11 + [_i, _i, _i, _i, _p]),
+    "clhip_proj_adam_multi": (_i, [_i, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _i, _p]),
     "clhip_vit_set_sdlora": (_i, [_p, _i, _p, _p, _p, _p]),
     "clhip_vit_sdlora_refresh": (_i, [_p, C.POINTER(VitParams), _p, _p]),
     "clhip_vit_backward_sdlora": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
+    "clhip_vit_lora_refresh_ab": (_i, [_p, C.POINTER(VitParams), _p, _p]),
+    "clhip_vit_backward_lora_ab": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p]),
     "clhip_vit_set_prefix": (_i, [_p, _p, _p, _p]),
     "clhip_vit_backward_prefix": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),

@@ -284,6 +284,16 @@ extern "C" int clhip_vit_prep_weights(clhip_vit* v, const clhip_vit_params* P, v
     return CLHIP_OK;
 }
 
+extern "C" int clhip_vit_lora_refresh_ab(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream) {
+    // A and B both moved: the k / v rows of all layers' qkv copies in one launch; nothing else depends on them (clhip_lora_grad_ab packs its own operands)
+    CLHIP_CHECK_ARG(v && P && P->layers && shadow && v->d.lora_rank > 0);
+    for (int l = 0; l < v->d.depth; ++l) {
+        const clhip_vit_layer_params& p = P->layers[l];
+        CLHIP_CHECK_ARG(p.qkv_w && p.lora_a_k && p.lora_b_k && p.lora_a_v && p.lora_b_v);
+    }
+    return clhip_vit_prep_weights(v, P, shadow, 1, 1, stream);
+}
+
 extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* images, int B,
                                  const float* prompt_tokens, int n_prompt, int save, float* gram, float* feat, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && images && feat && B > 0 && n_prompt >= 0);
@@ -346,7 +356,8 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
 }
 
 static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream);
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream,
+                         float* const* d_ab = nullptr, void* ab_ws = nullptr);
 
 extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
                                           float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream) {
@@ -366,10 +377,18 @@ extern "C" int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P
     return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, nullptr, nullptr, dpk, dpv, stream);
 }
 
+extern "C" int clhip_vit_backward_lora_ab(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
+                                          float* const* d_factors, void* ab_ws, void* stream) {
+    CLHIP_CHECK_ARG(v && v->d.lora_rank > 0 && d_factors && ab_ws);
+    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, d_factors, ab_ws);
+}
+
 // d_sd (nullable): the SD-LoRA gradients, run where the lora_B gradients run (the two modes exclude each other).  dpk / dpv: the prefix gradients of a forward
 // that ran in prefix mode (required then, refused otherwise)
+// d_ab (nullable, with its scratch ab_ws): the gradients of all four LoRA factors of every layer (LoRA-Sub: A trains too), run where the lora_B gradients run.
 static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream) {
+                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream,
+                         float* const* d_ab, void* ab_ws) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && dfeat);
     CLHIP_CHECK_ARG(d_sd == nullptr || (v->sd_terms > 0 && d_lora_b == nullptr && v->last.sd_ws != 0));
     CLHIP_CHECK_ARG(d_adapter == nullptr || v->d.adapter_dim > 0);
@@ -378,10 +397,11 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
     const Layout& L = v->last;
     CLHIP_CHECK_ARG(dprompt_tokens == nullptr || L.P > 0);
     CLHIP_CHECK_ARG(d_lora_b == nullptr || d.lora_rank > 0);
+    CLHIP_CHECK_ARG(d_ab == nullptr || (d.lora_rank > 0 && ab_ws != nullptr && d_lora_b == nullptr && d_sd == nullptr));
     CLHIP_CHECK_ARG((dpk != nullptr) == !L.pf_lp.empty() && (dpk != nullptr) == (dpv != nullptr));
     CLHIP_CHECK_ARG(v->tap == nullptr || v->tap_cap >= tap_slot_off(v, L, v->d.depth, 0));
     int lowest = 0;                                            // the lowest layer whose attention backward somebody needs
-    if (dpk && !dprompt_tokens && !d_lora_b && !d_adapter && !d_sd)
+    if (dpk && !dprompt_tokens && !d_lora_b && !d_adapter && !d_sd && !d_ab)
         while (L.pf_lp[lowest] == 0) ++lowest;
     char* ws = static_cast<char*>(workspace);
     const char* sh = static_cast<const char*>(shadow);
@@ -395,7 +415,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
     // (inside a stream capture everything stays on the captured stream, as plan.hip does: no fork / join nodes, no stream probe)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(main_s, &cap);
-    const bool side_on = two_streams && (d_lora_b != nullptr || d_sd != nullptr) && cap == hipStreamCaptureStatusNone;
+    const bool side_on = two_streams && (d_lora_b != nullptr || d_sd != nullptr || d_ab != nullptr) && cap == hipStreamCaptureStatusNone;
     hipStream_t shared_side = side_on ? clhip_shared_stream(0, main_s, false) : nullptr;
     if (side_on && shared_side == nullptr) { clhip_set_error("clhip_vit_backward: cannot create the side stream"); return CLHIP_EHIP; }
     const bool first_side = side_on && !v->side;
@@ -478,6 +498,14 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
                 return clhip_sdlora_grad(ws + L.h1[l], ws + L.dqkv, v->sd_factors + (size_t)l * 4 * v->sd_terms, v->sd_ranks.data(), v->sd_terms, v->sd_mag,
                                          v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M,
                                          D, dt, ls);
+            }));
+        }
+        if (d_ab) {
+            float* const* ga = d_ab + 4 * l;
+            CLHIP_CHECK_ARG(p.lora_a_k && p.lora_b_k && p.lora_a_v && p.lora_b_v && ga[0] && ga[1] && ga[2] && ga[3]);
+            TRY(leaf([&](void* ls) {
+                return clhip_lora_grad_ab(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_b_k, p.lora_a_v, p.lora_b_v, ga[0], ga[1], ga[2], ga[3], ab_ws, M, D,
+                                          d.lora_rank, dt, ls);
             }));
         }
         if (l == lowest && dprompt_tokens == nullptr) break;      // nothing below the first block (or the lowest prefixed one) needs a gradient

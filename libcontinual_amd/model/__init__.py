@@ -15,6 +15,7 @@ from .inflora_opt import InfLoRA_OPT  # noqa: F401
 from .inflora import InfLoRA  # noqa: F401
 from .ranpac import RanPAC, RPClassifier  # noqa: F401
 from .sd_lora import SD_LoRA  # noqa: F401
+from .lora_sub import LoRAsub_DRS  # noqa: F401
 from .codaprompt import CodaPrompt  # noqa: F401
 from .dualprompt import DualPrompt  # noqa: F401
 from .heads import HipLinear  # noqa: F401

@@ -9,6 +9,7 @@ kwargs and plugin code written against it keep working:
         [ffn_adapt: transformer.blocks[i].adaptmlp.{down_proj, up_proj}   core/model/backbone/petl/vision_transformer_adapter.py:31-90]
     MultiHeadAttention_LoRA    transformer.py:199-274   (apply_lora, init_param, merge_weight, reset_input_matrix, cur_matrix)
     MultiHeadAttention_SDLoRA  transformer.py:276-357   (lora_{A,B}_{q,v}_list, mag_lora, assimilated_mag_lora_{q,v}, init_param)
+    MultiHeadAttention_LoRA_Sub transformer.py:359-444  (lora_{A,B}_{k,v}, prev_{k,v}_weight, init_param, save_weight, reset_input_matrix, cur_matrix)
     L2PPrompt                  core/model/backbone/prompt.py:345-406 (prompt, prompt_key)
     CodaPromptPool             core/model/backbone/prompt.py:37-223  (e_p_{l}, e_k_{l}, e_a_{l}, task_count, process_task_count, gram_schmidt)
     DualPromptPool             core/model/backbone/prompt.py:231-337 (g_p_{l}, e_p_{l}, e_k_{l}, task_count, process_task_count)
@@ -151,6 +152,48 @@ class MultiHeadAttention_LoRA(MultiHeadAttention):
         self.cur_matrix.zero_()
 
 
+class MultiHeadAttention_LoRA_Sub(MultiHeadAttention_LoRA):
+    """transformer.py:359-444: LoRA on k and v whose finished terms are kept in the buffers `prev_k_weight` / `prev_v_weight` [D, D] instead of being merged
+    into the pretrained weight, which is never modified.  The k / v rows of the qkv weight take three forms: W - prev for the Gram pass of `before_task`
+    (the "subtraction"), (W + prev) + B A while `apply_lora` (training: A and B both train), W + prev otherwise.  The executor reads one of two composed
+    fp32 masters (`executor_weight`), rebuilt on the device whenever W or prev changed -- once per task, plain torch."""
+
+    def __init__(self, dim, num_heads, lora_rank=10, lora_bias=False, **kw):
+        if lora_bias:
+            raise NotImplementedError("lora_bias: true -- the effective-weight form W + B A has no place for the factors' biases")
+        super().__init__(dim, num_heads, lora_rank=lora_rank)
+        self.register_buffer("prev_k_weight", torch.zeros(dim, dim))
+        self.register_buffer("prev_v_weight", torch.zeros(dim, dim))
+        self.register_buffer("_w_plus", torch.zeros(3 * dim, dim), persistent=False)
+        self.register_buffer("_w_minus", torch.zeros(3 * dim, dim), persistent=False)
+        self.subtract = False            # True during the Gram pass: the executor reads W - prev
+        self._composed = None
+
+    @torch.no_grad()
+    def executor_weight(self):
+        """the composed master the executor's qkv_w points at: W - prev while `subtract`, else W + prev"""
+        w = self.qkv.weight
+        sig = (w.data_ptr(), w._version, self.prev_k_weight.data_ptr(), self.prev_k_weight._version, self.prev_v_weight.data_ptr(),
+               self.prev_v_weight._version, self._w_plus.data_ptr())
+        if self._composed != sig:
+            D = self.dim
+            for dst, sign in ((self._w_plus, 1.0), (self._w_minus, -1.0)):
+                dst.copy_(w)
+                dst[D:2 * D].add_(self.prev_k_weight, alpha=sign)
+                dst[2 * D:].add_(self.prev_v_weight, alpha=sign)
+            self._composed = sig
+        return self._w_minus if self.subtract else self._w_plus
+
+    @torch.no_grad()
+    def save_weight(self):
+        self.prev_k_weight += self.lora_B_k.weight @ self.lora_A_k.weight
+        self.prev_v_weight += self.lora_B_v.weight @ self.lora_A_v.weight
+        self.apply_lora = False
+
+    def merge_weight(self):
+        raise NotImplementedError("LoRA-Sub keeps its finished terms in prev_k_weight / prev_v_weight (save_weight); the pretrained weight is never modified")
+
+
 class MultiHeadAttention_SDLoRA(MultiHeadAttention):
     """transformer.py:276-357: on q and v a sum over the tasks so far of low-rank terms, the past ones normalised to unit Frobenius norm, each scaled
     by a trainable scalar of `mag_lora` (a ParameterList the method assigns, the same object in every block).  The lists hold parameter holders, so
@@ -234,7 +277,7 @@ class _PatchEmbed(nn.Module):
 
 
 _ATTN = {"MultiHeadAttention": MultiHeadAttention, "MultiHeadAttention_LoRA": MultiHeadAttention_LoRA,
-         "MultiHeadAttention_SDLoRA": MultiHeadAttention_SDLoRA}
+         "MultiHeadAttention_SDLoRA": MultiHeadAttention_SDLoRA, "MultiHeadAttention_LoRA_Sub": MultiHeadAttention_LoRA_Sub}
 
 
 class _Scratch:
@@ -294,6 +337,24 @@ class _VitSdFn(torch.autograd.Function):
         if vit._fwd_token != ctx.token:
             raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
         return (None, None, None) + tuple(vit._run_backward_sd(dfeat))
+
+
+class _VitAbFn(torch.autograd.Function):
+    """features = ViT(images) in LoRA-Sub mode; `params` = A_k, B_k, A_v, B_v per layer: backward -> their gradients (transformer.py:415-418 under
+    autograd in the reference)"""
+
+    @staticmethod
+    def forward(ctx, vit, images, need, *params):
+        feat = vit._run_forward(images, None, need, None)
+        ctx.vit, ctx.token = vit, vit._fwd_token
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        vit = ctx.vit
+        if vit._fwd_token != ctx.token:
+            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        return (None, None, None) + tuple(vit._run_backward_ab(dfeat))
 
 
 class _CodaFn(torch.autograd.Function):
@@ -409,13 +470,16 @@ class VisionTransformer(nn.Module):
         self.img_size, self.patch_size, self.embed_dim, self.depth, self.num_heads = img_size, patch_size, embed_dim, depth, num_heads
         self.num_features = embed_dim
         self.mlp_dim = int(embed_dim * mlp_ratio)
-        self.lora_rank = lora_rank if attn_layer is MultiHeadAttention_LoRA else 0
+        self.lora_sub = attn_layer is MultiHeadAttention_LoRA_Sub
+        self.lora_rank = lora_rank if attn_layer is MultiHeadAttention_LoRA or self.lora_sub else 0
         self.compute_dtype = dtype
         self.patch_embed = _PatchEmbed(img_size, patch_size, in_chans, embed_dim)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + 1, embed_dim))
         self.sd_lora = attn_layer is MultiHeadAttention_SDLoRA
         kw = {"lora_rank": lora_rank} if self.lora_rank or self.sd_lora else {}
+        if self.lora_sub:
+            kw["lora_bias"] = kwargs.get("lora_bias", False)
         self.transformer = Transformer(embed_dim, depth, num_heads, mlp_ratio, attn_layer, **kw)
         self.norm = _P((embed_dim,))
         self._s = _Scratch()
@@ -465,10 +529,14 @@ class VisionTransformer(nn.Module):
         """down w, down b, up w, up b of every layer, in layer order (empty without adapters)"""
         return [t for b in self.transformer.blocks for t in b.adaptmlp.tensors()] if self.adapter_dim else []
 
+    def _qkv_master(self, b):
+        """the fp32 qkv weight the executor reads for block b: the parameter itself, or LoRA-Sub's composed W +- prev"""
+        return b.attn.executor_weight() if self.lora_sub else b.attn.qkv.weight
+
     def _frozen_tensors(self):
         out = [self.patch_embed.proj.weight]
         for b in self.transformer.blocks:
-            out += [b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight]
+            out += [self._qkv_master(b), b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight]
         return out
 
     def _all_tensors(self):
@@ -488,6 +556,8 @@ class VisionTransformer(nn.Module):
             s.sig = None
         # parameter pointer table + staleness signature of the compute-dtype weight copies
         ptrs = tuple(p.data_ptr() for p in self._all_tensors())
+        if self.lora_sub:
+            ptrs += tuple(self._qkv_master(b).data_ptr() for b in self.transformer.blocks)
         if s.cparams is None or s.keep != ptrs:
             for p in self._all_tensors():
                 require_gpu(p)
@@ -496,7 +566,7 @@ class VisionTransformer(nn.Module):
             layers = (_lib.VitLayerParams * self.depth)()
             for i, b in enumerate(self.transformer.blocks):
                 L = layers[i]
-                L.qkv_w, L.qkv_b = b.attn.qkv.weight.data_ptr(), b.attn.qkv.bias.data_ptr()
+                L.qkv_w, L.qkv_b = self._qkv_master(b).data_ptr(), b.attn.qkv.bias.data_ptr()
                 L.proj_w, L.proj_b = b.attn.proj.weight.data_ptr(), b.attn.proj.bias.data_ptr()
                 L.ln1_w, L.ln1_b = b.ln_1.weight.data_ptr(), b.ln_1.bias.data_ptr()
                 L.fc1_w, L.fc1_b = b.mlp.fc1.weight.data_ptr(), b.mlp.fc1.bias.data_ptr()
@@ -515,7 +585,9 @@ class VisionTransformer(nn.Module):
         if lora_on and not all(a.apply_lora for a in self.attention_modules()):
             raise _lib.ClhipError("apply_lora must be set on all attention layers or none")
         frozen = self._frozen_tensors()
-        if self.lora_rank:            # lora_A is fixed within a task: a change (init_param / SVD in before_task) forces the full preparation
+        if self.lora_sub and lora_on and any(a.subtract for a in self.attention_modules()):
+            raise _lib.ClhipError("the Gram pass on W - prev runs without the LoRA term (transformer.py:407-413): clear apply_lora or subtract")
+        if self.lora_rank and not self.lora_sub:   # lora_A is fixed within a task: a change (init_param / SVD in before_task) forces the full preparation
             for a in self.attention_modules():
                 frozen = frozen + [a.lora_A_k.weight, a.lora_A_v.weight]
         if self.sd_lora:
@@ -524,6 +596,9 @@ class VisionTransformer(nn.Module):
         if s.sig != sig:
             call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), int(lora_on), 0, _st())
             s.sig = sig
+        elif lora_on and self.lora_sub:
+            # A and B both move every optimizer step: the k / v rows of the qkv copies, nothing else is re-rounded
+            call("clhip_vit_lora_refresh_ab", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), _st())
         elif lora_on:
             # lora_B moves every optimizer step: refresh only the effective qkv copies (transformer.py:249-255)
             call("clhip_vit_prep_weights", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), 1, 1, _st())
@@ -610,6 +685,27 @@ class VisionTransformer(nn.Module):
         call("clhip_vit_backward_sdlora", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, arr,
              rows.data_ptr(), dmag.data_ptr(), _st())
         return grads + [dmag[i:i + 1] for i in range(T1)]
+
+    def _run_backward_ab(self, dfeat):
+        """-> d A_k, d B_k, d A_v, d B_v of every layer (LoRA-Sub), views of one buffer that is reused from step to step"""
+        s = self._s
+        B, n_prompt = self._last
+        dfeat = dfeat.float().contiguous()
+        dev, D, r = dfeat.device, self.embed_dim, self.lora_rank
+        M = B * (n_prompt + 1 + self.patch_embed.num_patches)
+        flat = getattr(s, "ab_grads", None)
+        if flat is None or flat.device != dev:
+            flat = s.ab_grads = torch.empty(self.depth, 4 * r * D, device=dev)          # the kernels write every element
+        need = _lib.lib().clhip_lora_grad_ab_ws_bytes(M, D)
+        if getattr(s, "ab_ws", None) is None or s.ab_ws.device != dev or s.ab_ws.numel() < need:
+            s.ab_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        grads = []
+        for row in flat.unbind(0):
+            grads += [row[:r * D].view(r, D), row[r * D:2 * r * D].view(D, r), row[2 * r * D:3 * r * D].view(r, D), row[3 * r * D:].view(D, r)]
+        arr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in grads])
+        call("clhip_vit_backward_lora_ab", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, arr,
+             s.ab_ws.data_ptr(), _st())
+        return grads
 
     def _workspace(self, s, B, n_prompt, save, dev):
         """`save`: bit 0 = keep what the backward needs, bit 1 = keep every layer's attention input for the Gram launch"""
@@ -756,6 +852,12 @@ class VisionTransformer(nn.Module):
             params = self.sd_trainable()
             need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
             return _VitSdFn.apply(self, images, need, *params)
+        if self.lora_sub and any(a.apply_lora for a in self.attention_modules()):
+            if prompt_tokens is not None or get_input_matrix:
+                raise NotImplementedError("LoRA-Sub trains without prompt tokens, and its Gram pass runs on W - prev without the LoRA term")
+            params = [w for a in self.attention_modules() for w in (a.lora_A_k.weight, a.lora_B_k.weight, a.lora_A_v.weight, a.lora_B_v.weight)]
+            need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
+            return _VitAbFn.apply(self, images, need, *params)
         lora_b = []
         if self.lora_rank and any(a.apply_lora for a in self.attention_modules()):
             for a in self.attention_modules():

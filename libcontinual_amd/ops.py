@@ -388,6 +388,51 @@ def ncm_classify(feats, means):
     return pred
 
 
+# ------------------------------------------------------------------------------------------ LoRA-Sub-DRS (csrc/lorasub.hip)
+def atl(feats, labels, protos, margin, weight, df=None):
+    """AugmentedTripletLoss (lora_sub.py:34-68) on un-normalised features [B, D] and prototypes [P, D] (None or empty: no prototypes)
+    -> (loss [1], unweighted; df [B, D] = weight * d loss / d feats)"""
+    feats = _f32c(feats)
+    _dev(feats, labels)
+    B, D = feats.shape
+    P = 0 if protos is None else protos.shape[0]
+    protos = _f32c(protos) if P else None
+    labels = labels.to(torch.int64).contiguous()
+    loss = torch.empty(1, device=feats.device, dtype=torch.float32)
+    df = torch.empty_like(feats) if df is None else df
+    ws = torch.empty(max(1, _lib.lib().clhip_atl_ws_bytes(B, P)), device=feats.device, dtype=torch.uint8)
+    call("clhip_atl", _ptr(feats), _ptr(labels), _ptr(protos), B, D, P, float(margin), float(weight), _ptr(loss), _ptr(df), _ptr(ws), _st())
+    return loss, df
+
+
+def lora_grad_ab(x, dqkv, a_k, b_k, a_v, b_v, outs=None):
+    """gradients of the four k / v factors of one layer: x [M, D], dqkv [M, 3D] in the compute dtype -> (d_a_k, d_b_k, d_a_v, d_b_v), written"""
+    _dev(x, dqkv, a_k, b_k, a_v, b_v)
+    (M, D), r = x.shape, a_k.shape[0]
+    assert x.dtype == dqkv.dtype and x.is_contiguous() and dqkv.is_contiguous() and dqkv.shape == (M, 3 * D)
+    assert a_k.shape == a_v.shape == (r, D) and b_k.shape == b_v.shape == (D, r)
+    if outs is None:
+        outs = [torch.empty_like(t, dtype=torch.float32) for t in (a_k, b_k, a_v, b_v)]
+    ws = torch.empty(_lib.lib().clhip_lora_grad_ab_ws_bytes(M, D), device=x.device, dtype=torch.uint8)
+    call("clhip_lora_grad_ab", _ptr(x), _ptr(dqkv), *[_ptr(_f32c(t)) for t in (a_k, b_k, a_v, b_v)], *[_ptr(o) for o in outs], _ptr(ws), M, D, r,
+         _lib.BF16 if x.dtype == torch.bfloat16 else _lib.F32, _st())
+    return tuple(outs)
+
+
+def proj_adam_table(tensors):
+    """device pointer table [count, 4] of (p, g, m, v) for proj_adam_multi; the tensors must outlive it"""
+    for row in tensors:
+        _dev(*row)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in row)
+    return torch.tensor([[t.data_ptr() for t in row] for row in tensors], dtype=torch.int64).to(tensors[0][0].device)
+
+
+def proj_adam_multi(table, transforms, ws, D, rank, lr, beta1, beta2, eps, weight_decay, step):
+    """the projected Adam step of lora_sub.py:120-157 over table.shape[0] = 4 * layers factor tensors (per layer A_k, B_k, A_v, B_v); transforms: int64
+    device tensor [layers] of pointers to T_l [D, D] fp32, or None for plain Adam; ws: table.shape[0] * D * rank floats (unused without transforms)"""
+    call("clhip_proj_adam_multi", table.shape[0], _ptr(table), _ptr(transforms), _ptr(ws), D, rank, float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), int(step), _st())
+
 
 # ------------------------------------------------------------------------------------------ RanPAC (csrc/rp.hip: exact fp32 on the f32-input MFMA)
 def rp_project(feats, w_rand, relu=True):

@@ -446,6 +446,12 @@ class Trainer:
                 model.before_task(task_idx, self.buffer, self.train_loader.get_loader(task_idx), self.test_loader.get_loader(task_idx))
             self.log(f"Trainable Parameters for Task {task_idx} : {count_parameters(model)} / {count_all_parameters(model)}")
             _, _, self.optimizer, self.scheduler = self._init_optim(self.config)
+            if method_name == "LoRAsub_DRS":
+                if self.distribute:
+                    raise NotImplementedError("LoRAsub_DRS: n_gpu > 1 is not covered (its projected Adam has no gradient exchange)")
+                # core/trainer.py:324-327: the plugin's own projected Adam, built after before_task, under the cosine schedule over the task's epochs
+                self.optimizer = model.get_optimizer(self.config["optimizer"]["kwargs"]["lr"], self.config["optimizer"]["kwargs"]["weight_decay"])
+                self.scheduler = sched.CosineSchedule(self.optimizer, K=self.config["epoch"])
             dataloader = self.train_loader.get_loader(task_idx)
             val_bias_dataloader = None
             if method_name == "bic":
@@ -493,7 +499,8 @@ class Trainer:
                 self.log(f"Epoch [{epoch_idx}/{n_epoch}] Learning Rate {self.scheduler.get_last_lr()}\t|\tLoss: {loss:.4f} "
                          f"\tAverage Acc: {acc1:.2f} \t{n_img / dt:.0f} img/s")
                 self.last_epoch_stats = dict(task=task_idx, epoch=epoch_idx, loss=loss, acc1=acc1, images_per_sec=n_img / dt)
-                if (epoch_idx + 1) % self.val_per_epoch == 0 or (epoch_idx + 1) == self.inc_epoch:
+                # (core/trainer.py:366-377: LoRAsub_DRS classifies by prototypes, which task 0 has only after after_task -- no in-epoch validation)
+                if method_name != "LoRAsub_DRS" and ((epoch_idx + 1) % self.val_per_epoch == 0 or (epoch_idx + 1) == self.inc_epoch):
                     test_acc = self._validate(task_idx)
                     batch_last_acc, per_task_acc = test_acc["avg_acc"], test_acc["per_task_acc"]
                     best_batch_last_acc = max(batch_last_acc, best_batch_last_acc)
