@@ -806,50 +806,57 @@ int clhip_vit_prep_weights(clhip_vit* v, const clhip_vit_params* P, void* shadow
  * prompt tokens (n_prompt > 0) or at the cls token; gram (nullable) [depth, D, D] += X^T X of every attention input */
 int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* images, int B,
                       const float* prompt_tokens, int n_prompt, int save_for_backward, float* gram, float* feat, void* stream);
-/* after a forward with save_for_backward: dprompt_tokens [n_prompt, D] (nullable); d_lora_b (nullable): [2*depth] pointers
- * (k, v per layer) accumulated into */
-int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
-                       float* dprompt_tokens, float* const* d_lora_b, void* stream);
+/* The backward of the last forward that ran with save_for_backward, and every parameter gradient of the ViT path.  Each member of clhip_vit_grads is nullable:
+ * NULL = that gradient is not asked for (out == NULL: none of them; the chain still runs).  Every argument rule is checked before the first launch.
+ * dprompt_tokens: [n_prompt, D], written; needs n_prompt > 0 in the saved forward.  Without it the chain stops after the lowest layer's attention backward.
+ * d_lora_b : [2*depth] pointers (k, v per layer) to [D, r], ACCUMULATED into; for a fixed A (InfLoRA; lora_rank > 0).  It reads the [A_k; A_v] operand that
+ *            clhip_vit_prep_weights packed, which clhip_vit_lora_refresh_ab does NOT refresh: it must not follow that call without a full prep_weights.
+ * d_adapter: [4*depth] pointers (d down_w [R, D], d down_b [R], d up_w [D, R], d up_b [D] per layer), written (adapter_dim > 0).  With adapters the input
+ *            gradient of every adapter branch is part of the chain either way.
+ * d_sd     : SD-LoRA (clhip_vit_set_sdlora): [4*depth] pointers (d A_q, d B_q, d A_v, d B_v of the current term per layer), written by clhip_sdlora_grad per
+ *            layer; requires d_mag_rows [depth, nterms] (scratch) and d_mag [nterms] = its rows summed in layer order, after the chain, on the caller's stream.
+ * d_ab     : LoRA-Sub-DRS (A and B both train): [4*depth] pointers (d A_k, d B_k, d A_v, d B_v of the layer), written by clhip_lora_grad_ab per layer; requires
+ *            ab_ws: clhip_lora_grad_ab_ws_bytes(M, D) bytes of the caller's, M = B * tokens of the saved forward (lora_rank > 0).
+ *            d_lora_b, d_sd and d_ab exclude one another.  They are leaves of the chain: outside a stream capture (and unless WGRAD_STREAM=0) they run on a
+ *            side stream, ordered by events against the one dqkv buffer; the caller's stream owns the gradients again when the call returns.
+ * dpk, dpv : the prefix gradients of a forward that ran in prefix mode (clhip_vit_set_prefix): both required for one, refused otherwise.  [depth] host arrays
+ *            of fp32 [B, Lp[l], D] buffers, written (entries of plain layers are ignored).  Without any other gradient the chain stops at the lowest
+ *            prefixed layer's attention backward. */
+typedef struct clhip_vit_grads {
+    float* dprompt_tokens;
+    float *const *d_lora_b, *const *d_adapter;
+    float *const *d_sd, *d_mag_rows, *d_mag;
+    float* const* d_ab;
+    void* ab_ws;
+    float *const *dpk, *const *dpv;
+} clhip_vit_grads;
+int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, const clhip_vit_grads* out,
+                       void* stream);
 /* adapter dropout of the NEXT clhip_vit_forward (and of the backward that follows it): probability p in [0, 1) and the 64-bit seed in device
  * memory (required iff p > 0; read when the kernels run, so it must stay alive until then).  The forward consumes the state: forwards after it
  * run without dropout until this is called again. */
 int clhip_vit_set_adapter_dropout(clhip_vit* v, const unsigned long long* seed, float p);
-/* clhip_vit_backward that also FILLS the adapter gradients: d_adapter = [4*depth] pointers (d down_w [R, D], d down_b [R], d up_w [D, R],
- * d up_b [D] per layer), nullable.  With adapters the input gradient of every adapter branch is part of the chain either way. */
-int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
-                               float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream);
 /* SD-LoRA mode of the executor (new entry points; descriptors and parameter tables are untouched, so every other caller gets the executor it had).
  * set_sdlora: nterms > 0 switches the mode on -- ranks (host, copied), factors = [depth] factor tables back to back, mag [nterms], inv [depth, 2,
  *          nterms] on the device, all alive until replaced; forwards that save for the backward then keep every layer's attention input.  nterms = 0
  *          switches it off.  Requires lora_rank == 0 in the descriptor.
  * sdlora_refresh: clhip_sdlora_refresh on the executor's qkv copies (after clhip_vit_prep_weights without LoRA, and then once per step).
- * backward_sdlora: clhip_vit_backward that also runs clhip_sdlora_grad per layer: d_factors = [4 * depth] pointers (d A_q, d B_q, d A_v, d B_v of the
- *          current term per layer), d_mag_rows [depth, nterms] scratch, d_mag [nterms] = its rows summed in layer order. */
+ *          Its gradients: the d_sd member of clhip_vit_grads. */
 int clhip_vit_set_sdlora(clhip_vit* v, int nterms, const int* ranks, const float* const* factors, const float* mag, const float* inv);
 int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream);
-int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                              float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream);
 /* LoRA-Sub-DRS: A and B of the k / v LoRA terms both train (lora_rank > 0; the layers' qkv_w point at the caller's composed fp32 masters).
  * lora_refresh_ab: the per-step refresh when A moves too -- the k / v rows of all layers' qkv copies (W + B A, one launch); the q rows and every other weight
  *   copy keep the rounding of the last clhip_vit_prep_weights.  The [A_k; A_v] operand of clhip_lora_grad is NOT refreshed: clhip_vit_backward's d_lora_b is
- *   for a fixed A (InfLoRA) and must not follow this call without a full clhip_vit_prep_weights.
- * backward_lora_ab: clhip_vit_backward that runs clhip_lora_grad_ab per layer: d_factors = [4 * depth] pointers (d A_k, d B_k, d A_v, d B_v of the layer, all
- *   written); ab_ws: clhip_lora_grad_ab_ws_bytes(M, D) bytes of the caller's, M = B * tokens of the saved forward. */
+ *   for a fixed A (InfLoRA) and must not follow this call without a full clhip_vit_prep_weights.  Its gradients: the d_ab member of clhip_vit_grads. */
 int clhip_vit_lora_refresh_ab(clhip_vit*, const clhip_vit_params* params, void* shadow, void* stream);
-int clhip_vit_backward_lora_ab(clhip_vit*, const clhip_vit_params* params, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                               float* const* d_factors, void* ab_ws, void* stream);
 /* Prefix mode of the executor (VisionTransformer.forward with `prompt`, transformer.py:2272-2288: blocks whose prompt is not None attend over
- * [prefix | tokens]).  New entry points; descriptors and parameter tables are untouched.
+ * [prefix | tokens]).  Descriptors and parameter tables are untouched.
  * set_prefix: Lp [depth] (host, copied; 0 = a plain layer, at least one > 0), pk / pv [depth] host arrays of device pointers to [B, Lp[l], D] in the
  *          compute dtype (copied; the BUFFERS are the caller's and must outlive the backward).  The state PERSISTS: every forward after it runs in prefix
  *          mode until Lp == NULL switches it off (CODA-Prompt's query pass runs with the mode off).  A forward remembers the prefixes it ran with, so
  *          switching afterwards does not disturb its backward.  The saved lse stays [B, H, N]; the workspace size does not change.
- * backward_prefix: clhip_vit_backward of a forward that ran in prefix mode (required for one, refused otherwise); also fills dpk / dpv = [depth] host
- *          arrays of fp32 [B, Lp[l], D] buffers (entries of plain layers are ignored).  Without other gradients the chain stops at the lowest
- *          prefixed layer's attention backward. */
+ *          Its gradients: the dpk / dpv members of clhip_vit_grads. */
 int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* const* pk, const void* const* pv);
-int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                              float* const* d_lora_b, float* const* dpk, float* const* dpv, void* stream);
 /* debug/test: copy one saved tensor of layer l of the last forward to fp32: 0 x_in [M, D] (layer == depth: the last block's output), 1 qkv [M, 3D],
  * 2 attn out, 3 x_mid, 4 GELU derivative of the mlp [M, mlp], 5 h1 = the LN1 output [M, D], 6 lse [B, H, N], 7 the LN1 statistics [2, M] (mean row, rstd
  * row), 8 the LN2 statistics likewise, 9 the adapter's dropped hidden rows [M, R].  0..4 and 6..9 need a forward that saved for the backward; 5 needs h1 to

@@ -44,6 +44,13 @@ class VitParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cls_token", "pos_embed", "pe_w", "pe_b", "norm_w", "norm_b")] + [("layers", C.POINTER(VitLayerParams))]
 
 
+class VitGrads(C.Structure):
+    """clhip_vit_grads (include/clhip.h): every member nullable; the pointer tables are (c_void_p * n) arrays"""
+    _fields_ = [("dprompt_tokens", C.c_void_p)] + [(n, C.POINTER(C.c_void_p)) for n in ("d_lora_b", "d_adapter", "d_sd")] + [
+        ("d_mag_rows", C.c_void_p), ("d_mag", C.c_void_p), ("d_ab", C.POINTER(C.c_void_p)), ("ab_ws", C.c_void_p),
+        ("dpk", C.POINTER(C.c_void_p)), ("dpv", C.POINTER(C.c_void_p))]
+
+
 def build(force=False):
     """Compile libclhip.so with hipcc for gfx950 (cross-compiles without a GPU)."""
     script = os.path.join(_HERE, "csrc", "build.sh")
@@ -204,13 +211,12 @@ _PROTOS = {
     "clhip_vit_workspace_bytes": (_sz, [_p, _i, _i, _i]),
     "clhip_vit_prep_weights": (_i, [_p, C.POINTER(VitParams), _p, _i, _i, _p]),
     "clhip_vit_forward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _i, _p, _i, _i, _p, _p, _p]),
-    "clhip_vit_backward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p]),
+    "clhip_vit_backward": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, C.POINTER(VitGrads), _p]),
     "clhip_vit_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
     "clhip_vit_set_tap": (_i, [_p, _p, _sz]),
     "clhip_vit_tap_floats": (_sz, [_p]),
     "clhip_vit_last_backward_info": (_i, [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "clhip_vit_set_adapter_dropout": (_i, [_p, _p, _f]),
-    "clhip_vit_backward_adapter": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _p]),
     "clhip_adapter_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _i, _i, _i, _i, _p]),
     "clhip_adapter_bwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _f, _i, _i, _i, _i, _p]),
     "clhip_adapter_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
@@ -227,11 +233,8 @@ _PROTOS = {
     "clhip_proj_adam_multi": (_i, [_i, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _i, _p]),
     "clhip_vit_set_sdlora": (_i, [_p, _i, _p, _p, _p, _p]),
     "clhip_vit_sdlora_refresh": (_i, [_p, C.POINTER(VitParams), _p, _p]),
-    "clhip_vit_backward_sdlora": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
     "clhip_vit_lora_refresh_ab": (_i, [_p, C.POINTER(VitParams), _p, _p]),
-    "clhip_vit_backward_lora_ab": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p]),
     "clhip_vit_set_prefix": (_i, [_p, _p, _p, _p]),
-    "clhip_vit_backward_prefix": (_i, [_p, C.POINTER(VitParams), _p, _p, _p, _p, C.POINTER(C.c_void_p), _p, _p, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -350,54 +350,21 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
     return clhip_ln_pool_fwd(ws + L.x_in[d.depth], P->norm_w, P->norm_b, feat, B, N, D, n_prompt > 0 ? n_prompt : 1, 1e-6f, dt, stream);
 }
 
-extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                                  float* const* d_lora_b, void* stream) {
-    return clhip_vit_backward_adapter(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, stream);
-}
-
-static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream,
-                         float* const* d_ab = nullptr, void* ab_ws = nullptr);
-
-extern "C" int clhip_vit_backward_adapter(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
-                                          float* dprompt_tokens, float* const* d_lora_b, float* const* d_adapter, void* stream) {
-    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, d_adapter, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int clhip_vit_backward_sdlora(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat,
-                                         float* dprompt_tokens, float* const* d_factors, float* d_mag_rows, float* d_mag, void* stream) {
-    CLHIP_CHECK_ARG(v && v->sd_terms > 0 && d_factors && d_mag_rows && d_mag);
-    TRY(backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, d_factors, d_mag_rows, nullptr, nullptr, stream));
-    return clhip_sdlora_mag_reduce(d_mag_rows, v->d.depth, v->sd_terms, d_mag, stream);
-}
-
-extern "C" int clhip_vit_backward_prefix(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                                         float* const* d_lora_b, float* const* dpk, float* const* dpv, void* stream) {
-    CLHIP_CHECK_ARG(v && dpk && dpv);
-    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, d_lora_b, nullptr, nullptr, nullptr, dpk, dpv, stream);
-}
-
-extern "C" int clhip_vit_backward_lora_ab(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                                          float* const* d_factors, void* ab_ws, void* stream) {
-    CLHIP_CHECK_ARG(v && v->d.lora_rank > 0 && d_factors && ab_ws);
-    return backward_impl(v, P, shadow, workspace, dfeat, dprompt_tokens, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, d_factors, ab_ws);
-}
-
-// d_sd (nullable): the SD-LoRA gradients, run where the lora_B gradients run (the two modes exclude each other).  dpk / dpv: the prefix gradients of a forward
-// that ran in prefix mode (required then, refused otherwise)
-// d_ab (nullable, with its scratch ab_ws): the gradients of all four LoRA factors of every layer (LoRA-Sub: A trains too), run where the lora_B gradients run.
-static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, float* dprompt_tokens,
-                         float* const* d_lora_b, float* const* d_adapter, float* const* d_sd, float* d_mag_rows, float* const* dpk, float* const* dpv, void* stream,
-                         float* const* d_ab, void* ab_ws) {
+// the leaves (d_lora_b, d_sd, d_ab) exclude one another; dpk / dpv are required exactly when the saved forward ran in prefix mode
+extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const void* shadow, void* workspace, const float* dfeat, const clhip_vit_grads* out,
+                                  void* stream) {
+    const clhip_vit_grads G = out ? *out : clhip_vit_grads{};
+    float* const dprompt_tokens = G.dprompt_tokens;
+    const auto d_lora_b = G.d_lora_b, d_adapter = G.d_adapter, d_sd = G.d_sd, d_ab = G.d_ab, dpk = G.dpk, dpv = G.dpv;
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && workspace && dfeat);
-    CLHIP_CHECK_ARG(d_sd == nullptr || (v->sd_terms > 0 && d_lora_b == nullptr && v->last.sd_ws != 0));
+    CLHIP_CHECK_ARG(d_sd == nullptr || (v->sd_terms > 0 && G.d_mag_rows && G.d_mag && d_lora_b == nullptr && v->last.sd_ws != 0));
     CLHIP_CHECK_ARG(d_adapter == nullptr || v->d.adapter_dim > 0);
     CLHIP_CHECK_ARG(v->have_last && v->last.save);
     const clhip_vit_desc& d = v->d;
     const Layout& L = v->last;
     CLHIP_CHECK_ARG(dprompt_tokens == nullptr || L.P > 0);
     CLHIP_CHECK_ARG(d_lora_b == nullptr || d.lora_rank > 0);
-    CLHIP_CHECK_ARG(d_ab == nullptr || (d.lora_rank > 0 && ab_ws != nullptr && d_lora_b == nullptr && d_sd == nullptr));
+    CLHIP_CHECK_ARG(d_ab == nullptr || (d.lora_rank > 0 && G.ab_ws != nullptr && d_lora_b == nullptr && d_sd == nullptr));
     CLHIP_CHECK_ARG((dpk != nullptr) == !L.pf_lp.empty() && (dpk != nullptr) == (dpv != nullptr));
     CLHIP_CHECK_ARG(v->tap == nullptr || v->tap_cap >= tap_slot_off(v, L, v->d.depth, 0));
     int lowest = 0;                                            // the lowest layer whose attention backward somebody needs
@@ -496,7 +463,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
             CLHIP_CHECK_ARG(gs[0] && gs[1] && gs[2] && gs[3]);
             TRY(leaf([&](void* ls) {
                 return clhip_sdlora_grad(ws + L.h1[l], ws + L.dqkv, v->sd_factors + (size_t)l * 4 * v->sd_terms, v->sd_ranks.data(), v->sd_terms, v->sd_mag,
-                                         v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M,
+                                         v->sd_inv + (size_t)l * 2 * v->sd_terms, gs[0], gs[1], gs[2], gs[3], G.d_mag_rows + (size_t)l * v->sd_terms, ws + L.sd_ws, M,
                                          D, dt, ls);
             }));
         }
@@ -504,7 +471,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
             float* const* ga = d_ab + 4 * l;
             CLHIP_CHECK_ARG(p.lora_a_k && p.lora_b_k && p.lora_a_v && p.lora_b_v && ga[0] && ga[1] && ga[2] && ga[3]);
             TRY(leaf([&](void* ls) {
-                return clhip_lora_grad_ab(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_b_k, p.lora_a_v, p.lora_b_v, ga[0], ga[1], ga[2], ga[3], ab_ws, M, D,
+                return clhip_lora_grad_ab(ws + L.h1[l], ws + L.dqkv, p.lora_a_k, p.lora_b_k, p.lora_a_v, p.lora_b_v, ga[0], ga[1], ga[2], ga[3], G.ab_ws, M, D,
                                           d.lora_rank, dt, ls);
             }));
         }
@@ -516,7 +483,7 @@ static int backward_impl(clhip_vit* v, const clhip_vit_params* P, const void* sh
     }
     if (dprompt_tokens) TRY(clhip_vit_prompt_grad(g, dprompt_tokens, B, N, L.P, D, dt, stream));
     if (lora_pending) (void)hipStreamWaitEvent(main_s, v->ev_l, 0);          // the caller's stream owns the gradients again
-    return CLHIP_OK;
+    return d_sd ? clhip_sdlora_mag_reduce(G.d_mag_rows, d.depth, v->sd_terms, G.d_mag, stream) : CLHIP_OK;
 }
 
 extern "C" int clhip_vit_read_act(clhip_vit* v, void* workspace, int layer, int which, float* out, void* stream) {

@@ -38,6 +38,30 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptrs(ts):
+    """a C array of the tensors' device pointers (None -> NULL)"""
+    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _layer_views(flat, shapes):
+    """flat [depth, sum of the shapes' sizes] -> one view of every shape per layer, in layer order"""
+    sizes = [math.prod(shape) for shape in shapes]
+    return [t.view(shape) for row in flat.unbind(0) for t, shape in zip(row.split(sizes), shapes)]
+
+
+def _prefix_tables(depth, layers, pk, pv):
+    """`prefix` of _run_forward from the prefixed layers and their [B, Lp, D] key / value tensors: (Lp, pk, pv), each [depth], 0 / None on a plain layer"""
+    lp, k_, v_ = [0] * depth, [None] * depth, [None] * depth
+    for l, k, v in zip(layers, pk, pv):
+        lp[l], k_[l], v_[l] = k.shape[1], k, v
+    return lp, k_, v_
+
+
+def _check_token(vit, token):
+    if vit._fwd_token != token:
+        raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+
+
 class _P(nn.Module):
     """parameter holder with nn.Linear-style attribute names"""
 
@@ -295,70 +319,34 @@ class _Scratch:
         self.sd_key = None        # SD-LoRA: identity of the term set the executor was told about, and its device tables
         self.sd_tab = self.sd_ranks = self.sd_mag = self.sd_inv = None
         self.prefix_on = False    # the executor's prefix mode (clhip_vit_set_prefix) as this module last left it
+        self.layers = None        # the per-layer parameter table `cparams` points to
+        self.ab_grads = self.ab_ws = None     # LoRA-Sub: the factor gradients [depth, 4 r D] and the scratch of clhip_lora_grad_ab, reused from step to step
 
     def __deepcopy__(self, memo):
         return _Scratch()
 
 
 class _VitFn(torch.autograd.Function):
-    """features = ViT(images [, prompt tokens]); backward -> d prompt tokens and / or d lora_B and / or the four adapter gradients of every
-    layer.  `params` = the n_lora lora_B weights, then the adapter tensors (down w, down b, up w, up b per layer)"""
+    """features = ViT(images [, prompt tokens]); backward -> the gradients `want` names (VisionTransformer._run_backward), d prompt tokens first, then those of
+    `params` in its order: "lora_b" the lora_B weights (k, v per layer) and / or "adapter" the adapter tensors (down w, down b, up w, up b per layer); "sd" A_q,
+    B_q, A_v, B_v of the current SD-LoRA term per layer, then the magnitudes (transformer.py:317-332 under autograd in the reference); "ab" A_k, B_k, A_v, B_v
+    per layer (LoRA-Sub, transformer.py:415-418)"""
 
     @staticmethod
-    def forward(ctx, vit, images, prompt_tokens, gram, need, n_lora, *params):
+    def forward(ctx, vit, images, prompt_tokens, gram, need, want, *params):
         feat = vit._run_forward(images, prompt_tokens, need, gram)
-        ctx.vit, ctx.n_lora, ctx.has_prompt = vit, n_lora, prompt_tokens is not None
-        ctx.n_adapter = len(params) - n_lora
-        ctx.token = vit._fwd_token
+        ctx.vit, ctx.token, ctx.want = vit, vit._fwd_token, want
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        vit = ctx.vit
-        if vit._fwd_token != ctx.token:
-            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
-        dprompt, dlora, dad = vit._run_backward(dfeat, ctx.has_prompt, ctx.n_lora > 0, ctx.n_adapter > 0)
-        return (None, None, dprompt, None, None, None) + tuple(dlora if dlora else ()) + tuple(dad if dad else ())
-
-
-class _VitSdFn(torch.autograd.Function):
-    """features = ViT(images) in SD-LoRA mode; `params` = A_q, B_q, A_v, B_v of the current term per layer, then the magnitudes: backward -> their
-    gradients (transformer.py:317-332 under autograd in the reference)"""
-
-    @staticmethod
-    def forward(ctx, vit, images, need, *params):
-        feat = vit._run_forward(images, None, need, None)
-        ctx.vit, ctx.token = vit, vit._fwd_token
-        return feat
-
-    @staticmethod
-    def backward(ctx, dfeat):
-        vit = ctx.vit
-        if vit._fwd_token != ctx.token:
-            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
-        return (None, None, None) + tuple(vit._run_backward_sd(dfeat))
-
-
-class _VitAbFn(torch.autograd.Function):
-    """features = ViT(images) in LoRA-Sub mode; `params` = A_k, B_k, A_v, B_v per layer: backward -> their gradients (transformer.py:415-418 under
-    autograd in the reference)"""
-
-    @staticmethod
-    def forward(ctx, vit, images, need, *params):
-        feat = vit._run_forward(images, None, need, None)
-        ctx.vit, ctx.token = vit, vit._fwd_token
-        return feat
-
-    @staticmethod
-    def backward(ctx, dfeat):
-        vit = ctx.vit
-        if vit._fwd_token != ctx.token:
-            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
-        return (None, None, None) + tuple(vit._run_backward_ab(dfeat))
+        _check_token(ctx.vit, ctx.token)
+        g = ctx.vit._run_backward(dfeat, ctx.want)
+        return (None, None, g.get("prompt"), None, None, None) + tuple(t for k in ("lora_b", "adapter", "sd", "ab") for t in g.get(k, ()))
 
 
 class _CodaFn(torch.autograd.Function):
-    """query pass (no prefix) -> prompt assembly (clhip_coda_fwd) -> prefixed forward; backward = clhip_vit_backward_prefix -> clhip_coda_bwd.
+    """query pass (no prefix) -> prompt assembly (clhip_coda_fwd) -> prefixed forward; backward = clhip_vit_backward (dpk, dpv) -> clhip_coda_bwd.
     `params` = K, A, P of every prompted layer, in layer order"""
 
     @staticmethod
@@ -372,13 +360,10 @@ class _CodaFn(torch.autograd.Function):
                 raise _lib.ClhipError("the CODA-Prompt pool must be contiguous fp32")
         e = torch.empty(2, n, B, Lp, D, device=dev, dtype=tdt)
         c = torch.empty(n, B, f_, device=dev)
-        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
         K, A, P = params[0::3], params[1::3], params[2::3]
-        call("clhip_coda_fwd", n, q.data_ptr(), arr(K), arr(A), arr(P), arr(e[0].unbind(0)), arr(e[1].unbind(0)), c.data_ptr(), B, D, pool, length, f_, code,
-             _st())
-        lp, pk, pv = [0] * vit.depth, [None] * vit.depth, [None] * vit.depth
-        for i, l in enumerate(layers):
-            lp[l], pk[l], pv[l] = Lp, e[0, i], e[1, i]
+        ek, ev = e[0].unbind(0), e[1].unbind(0)
+        call("clhip_coda_fwd", n, q.data_ptr(), _ptrs(K), _ptrs(A), _ptrs(P), _ptrs(ek), _ptrs(ev), c.data_ptr(), B, D, pool, length, f_, code, _st())
+        lp, pk, pv = _prefix_tables(vit.depth, layers, ek, ev)
         feat = vit._run_forward(images, None, need, None, prefix=(lp, pk, pv))
         ctx.vit, ctx.token, ctx.lp, ctx.layers, ctx.dims = vit, vit._fwd_token, lp, layers, (pool, length, s_, f_)
         ctx.keep = (q, c, e)                                             # e: the executor reads the prefixes again in the backward
@@ -388,23 +373,22 @@ class _CodaFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat):
         vit = ctx.vit
-        if vit._fwd_token != ctx.token:
-            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        _check_token(vit, ctx.token)
         q, c, _ = ctx.keep
         pool, length, s_, f_ = ctx.dims
         n, B, D = len(ctx.layers), q.shape[0], vit.embed_dim
-        dpk, dpv = vit._run_backward_prefix(dfeat, ctx.lp)
+        g = vit._run_backward(dfeat, prefix_lp=ctx.lp)
         params = ctx.params
         grads = [torch.zeros_like(t) for t in params]                    # rows outside [s, f) get no gradient
-        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
         ws = torch.empty(_lib.lib().clhip_coda_ws_bytes(n, B, s_, f_) // 4, device=q.device)
-        call("clhip_coda_bwd", n, q.data_ptr(), arr(params[0::3]), arr(params[1::3]), arr(params[2::3]), c.data_ptr(), arr([dpk[l] for l in ctx.layers]),
-             arr([dpv[l] for l in ctx.layers]), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]), ws.data_ptr(), B, D, pool, length, s_, f_, _st())
+        call("clhip_coda_bwd", n, q.data_ptr(), _ptrs(params[0::3]), _ptrs(params[1::3]), _ptrs(params[2::3]), c.data_ptr(),
+             _ptrs([g["dpk"][l] for l in ctx.layers]), _ptrs([g["dpv"][l] for l in ctx.layers]), _ptrs(grads[0::3]), _ptrs(grads[1::3]), _ptrs(grads[2::3]),
+             ws.data_ptr(), B, D, pool, length, s_, f_, _st())
         return (None,) * 8 + tuple(grads)
 
 
 class _DualFn(torch.autograd.Function):
-    """query pass (no prefix) -> prompt selection (clhip_dual_fwd) -> prefixed forward; backward = clhip_vit_backward_prefix -> clhip_dual_bwd.
+    """query pass (no prefix) -> prompt selection (clhip_dual_fwd) -> prefixed forward; backward = clhip_vit_backward (dpk, dpv) -> clhip_dual_bwd.
     -> (features, key loss [1]).  `params` = g_p of every G-layer, then e_k, e_p of every E-layer, in layer order"""
 
     @staticmethod
@@ -422,12 +406,10 @@ class _DualFn(torch.autograd.Function):
         cos = torch.empty(ne, B, size, device=dev)
         idx = torch.empty(ne, B, device=dev, dtype=torch.int32)
         loss = torch.zeros(1, device=dev)                                # (eval mode leaves it alone)
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        call("clhip_dual_fwd", ng, ne, q.data_ptr(), arr(g_p), arr(e_k), arr(e_p), arr([p[0] for p in pre]), arr([p[1] for p in pre]), cos.data_ptr(),
-             idx.data_ptr(), loss.data_ptr(), B, D, size, Lg, Le, int(train), int(task_id) if train else 0, code, _st())
-        lp, pk, pv = [0] * vit.depth, [None] * vit.depth, [None] * vit.depth
-        for i, l in enumerate(list(gl) + list(el)):
-            lp[l], pk[l], pv[l] = pre[i].shape[2], pre[i][0], pre[i][1]
+        ek, ev = [p[0] for p in pre], [p[1] for p in pre]
+        call("clhip_dual_fwd", ng, ne, q.data_ptr(), _ptrs(g_p), _ptrs(e_k), _ptrs(e_p), _ptrs(ek), _ptrs(ev), cos.data_ptr(), idx.data_ptr(), loss.data_ptr(), B, D,
+             size, Lg, Le, int(train), int(task_id) if train else 0, code, _st())
+        lp, pk, pv = _prefix_tables(vit.depth, list(gl) + list(el), ek, ev)
         feat = vit._run_forward(images, None, need, None, prefix=(lp, pk, pv))
         pool.last_cos, pool.last_idx = cos, idx
         ctx.vit, ctx.token, ctx.lp, ctx.pool, ctx.task_id, ctx.train = vit, vit._fwd_token, lp, pool, task_id, train
@@ -438,8 +420,7 @@ class _DualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat, dloss):
         vit, pool = ctx.vit, ctx.pool
-        if vit._fwd_token != ctx.token:
-            raise RuntimeError("the ViT workspace was overwritten by a later forward before this backward ran")
+        _check_token(vit, ctx.token)
         if not ctx.train:
             raise RuntimeError("DualPrompt: the inference selection (arg-max over the keys) has no backward")
         q, _ = ctx.keep
@@ -448,13 +429,13 @@ class _DualFn(torch.autograd.Function):
         if dfeat is None:
             dfeat = torch.zeros(B, D, device=q.device)
         dloss = torch.zeros(1, device=q.device) if dloss is None else dloss.float().reshape(1).contiguous()
-        dpk, dpv = vit._run_backward_prefix(dfeat, ctx.lp)
+        g = vit._run_backward(dfeat, prefix_lp=ctx.lp)
         params = ctx.params
         grads = [torch.zeros_like(t) for t in params]                    # rows other than task_id get no gradient
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         order = list(gl) + list(el)
-        call("clhip_dual_bwd", ng, ne, q.data_ptr(), arr(params[ng::2]), arr([dpk[l] for l in order]), arr([dpv[l] for l in order]), dloss.data_ptr(),
-             arr(grads[:ng]), arr(grads[ng::2]), arr(grads[ng + 1::2]), B, D, pool.e_pool_size, pool.g_p_length, pool.e_p_length, int(ctx.task_id), _st())
+        call("clhip_dual_bwd", ng, ne, q.data_ptr(), _ptrs(params[ng::2]), _ptrs([g["dpk"][l] for l in order]), _ptrs([g["dpv"][l] for l in order]),
+             dloss.data_ptr(), _ptrs(grads[:ng]), _ptrs(grads[ng::2]), _ptrs(grads[ng + 1::2]), B, D, pool.e_pool_size, pool.g_p_length, pool.e_p_length,
+             int(ctx.task_id), _st())
         return (None,) * 6 + tuple(grads)
 
 
@@ -579,7 +560,7 @@ class VisionTransformer(nn.Module):
                     L.ad_down_w, L.ad_down_b, L.ad_up_w, L.ad_up_b = [t.data_ptr() for t in b.adaptmlp.tensors()]
             cp = _lib.VitParams(self.cls_token.data_ptr(), self.pos_embed.data_ptr(), self.patch_embed.proj.weight.data_ptr(),
                                 self.patch_embed.proj.bias.data_ptr(), self.norm.weight.data_ptr(), self.norm.bias.data_ptr(), layers)
-            s.cparams, s.keep, s._layers = cp, ptrs, layers
+            s.cparams, s.keep, s.layers = cp, ptrs, layers
             s.sig = None
         lora_on = bool(self.lora_rank) and any(a.apply_lora for a in self.attention_modules())
         if lora_on and not all(a.apply_lora for a in self.attention_modules()):
@@ -671,42 +652,6 @@ class VisionTransformer(nn.Module):
         call("clhip_vit_sdlora_refresh", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), _st())
         return s
 
-    def _run_backward_sd(self, dfeat):
-        s = self._s
-        dfeat = dfeat.float().contiguous()
-        dev, D, T1 = dfeat.device, self.embed_dim, self.sd_terms()
-        r = self.attention_modules()[0].lora_A_q_list[-1].weight.shape[0]
-        flat = torch.empty(self.depth, 4 * r * D, device=dev)                          # the kernels write every element
-        grads = []
-        for row in flat.unbind(0):
-            grads += [row[:r * D].view(r, D), row[r * D:2 * r * D].view(D, r), row[2 * r * D:3 * r * D].view(r, D), row[3 * r * D:].view(D, r)]
-        arr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in grads])
-        rows, dmag = torch.empty(self.depth, T1, device=dev), torch.empty(T1, device=dev)
-        call("clhip_vit_backward_sdlora", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, arr,
-             rows.data_ptr(), dmag.data_ptr(), _st())
-        return grads + [dmag[i:i + 1] for i in range(T1)]
-
-    def _run_backward_ab(self, dfeat):
-        """-> d A_k, d B_k, d A_v, d B_v of every layer (LoRA-Sub), views of one buffer that is reused from step to step"""
-        s = self._s
-        B, n_prompt = self._last
-        dfeat = dfeat.float().contiguous()
-        dev, D, r = dfeat.device, self.embed_dim, self.lora_rank
-        M = B * (n_prompt + 1 + self.patch_embed.num_patches)
-        flat = getattr(s, "ab_grads", None)
-        if flat is None or flat.device != dev:
-            flat = s.ab_grads = torch.empty(self.depth, 4 * r * D, device=dev)          # the kernels write every element
-        need = _lib.lib().clhip_lora_grad_ab_ws_bytes(M, D)
-        if getattr(s, "ab_ws", None) is None or s.ab_ws.device != dev or s.ab_ws.numel() < need:
-            s.ab_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        grads = []
-        for row in flat.unbind(0):
-            grads += [row[:r * D].view(r, D), row[r * D:2 * r * D].view(D, r), row[2 * r * D:3 * r * D].view(r, D), row[3 * r * D:].view(D, r)]
-        arr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in grads])
-        call("clhip_vit_backward_lora_ab", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, arr,
-             s.ab_ws.data_ptr(), _st())
-        return grads
-
     def _workspace(self, s, B, n_prompt, save, dev):
         """`save`: bit 0 = keep what the backward needs, bit 1 = keep every layer's attention input for the Gram launch"""
         key = (B, n_prompt, int(save))
@@ -736,8 +681,7 @@ class VisionTransformer(nn.Module):
         feat = torch.empty(B, self.embed_dim, device=dev, dtype=torch.float32)
         if prefix is not None:
             lp, pk, pv = prefix
-            ptr = lambda ts: (C.c_void_p * self.depth)(*[None if t is None else t.data_ptr() for t in ts])
-            call("clhip_vit_set_prefix", s.handle, (C.c_int * self.depth)(*lp), ptr(pk), ptr(pv))
+            call("clhip_vit_set_prefix", s.handle, (C.c_int * self.depth)(*lp), _ptrs(pk), _ptrs(pv))
             s.prefix_on = True
         elif s.prefix_on:                                    # the mode persists in the executor: every other forward runs without it
             call("clhip_vit_set_prefix", s.handle, None, None, None)
@@ -754,42 +698,46 @@ class VisionTransformer(nn.Module):
         self._last = (B, n_prompt)
         return feat
 
-    def _run_backward(self, dfeat, want_prompt, want_lora, want_adapter=False):
+    def _run_backward(self, dfeat, want=(), prefix_lp=None):
+        """the backward of the last saving forward, one clhip_vit_backward -> {name: gradient(s)}.  want: names among "prompt" [n_prompt, D]; "lora_b" [D, r] k, v per
+        layer; "adapter" d down w, down b, up w, up b per layer; "sd" d A_q, B_q, A_v, B_v of the current term per layer, then one [1] slice per magnitude; "ab" d A_k,
+        B_k, A_v, B_v per layer (views of one buffer that is reused from step to step).  prefix_lp: Lp [depth] of a prefixed forward, which adds "dpk" / "dpv": per
+        layer a fp32 [B, Lp, D] tensor, None where Lp = 0"""
         s = self._s
         B, n_prompt = self._last
         dfeat = dfeat.float().contiguous()
-        dev = dfeat.device
-        dprompt = torch.empty(n_prompt, self.embed_dim, device=dev) if want_prompt else None
-        dl, arr = None, None
-        if want_lora:
-            dl = list(torch.zeros(2 * self.depth, self.embed_dim, self.lora_rank, device=dev).unbind(0))     # one fill, 2*depth views
-            arr = (C.c_void_p * (2 * self.depth))(*[t.data_ptr() for t in dl])
-        if not want_adapter:
-            call("clhip_vit_backward", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
-                 dprompt.data_ptr() if want_prompt else None, arr, _st())
-            return dprompt, dl, None
-        D, R = self.embed_dim, self.adapter_dim
-        flat = torch.empty(self.depth, 2 * R * D + R + D, device=dev)                  # the kernels write every element
-        dad = []
-        for row in flat.unbind(0):
-            dad += [row[:R * D].view(R, D), row[R * D:R * D + R], row[R * D + R:2 * R * D + R].view(D, R), row[2 * R * D + R:]]
-        aarr = (C.c_void_p * (4 * self.depth))(*[t.data_ptr() for t in dad])
-        call("clhip_vit_backward_adapter", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(),
-             dprompt.data_ptr() if want_prompt else None, arr, aarr, _st())
-        return dprompt, dl, dad
-
-    def _run_backward_prefix(self, dfeat, lp):
-        """-> (dpk, dpv): per layer a fp32 [B, Lp, D] tensor, None where Lp = 0"""
-        s = self._s
-        B, _ = self._last
-        dfeat = dfeat.float().contiguous()
-        dev = dfeat.device
-        dpk = [torch.empty(B, n, self.embed_dim, device=dev) if n else None for n in lp]          # the kernels write every element
-        dpv = [torch.empty(B, n, self.embed_dim, device=dev) if n else None for n in lp]
-        ptr = lambda ts: (C.c_void_p * self.depth)(*[None if t is None else t.data_ptr() for t in ts])
-        call("clhip_vit_backward_prefix", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), None, None, ptr(dpk), ptr(dpv),
-             _st())
-        return dpk, dpv
+        dev, D, depth = dfeat.device, self.embed_dim, self.depth
+        out, G = {}, _lib.VitGrads()
+        if "prompt" in want:
+            out["prompt"] = torch.empty(n_prompt, D, device=dev)
+            G.dprompt_tokens = out["prompt"].data_ptr()
+        if "lora_b" in want:
+            out["lora_b"] = list(torch.zeros(2 * depth, D, self.lora_rank, device=dev).unbind(0))            # one fill, 2*depth views
+            G.d_lora_b = _ptrs(out["lora_b"])
+        if "adapter" in want:                                # (the kernels write every element of the adapter, SD-LoRA, LoRA-Sub and prefix gradients)
+            R = self.adapter_dim
+            out["adapter"] = _layer_views(torch.empty(depth, 2 * R * D + R + D, device=dev), [(R, D), (R,), (D, R), (D,)])
+            G.d_adapter = _ptrs(out["adapter"])
+        if "sd" in want:
+            T1, r = self.sd_terms(), self.attention_modules()[0].lora_A_q_list[-1].weight.shape[0]
+            fac = _layer_views(torch.empty(depth, 4 * r * D, device=dev), [(r, D), (D, r)] * 2)
+            rows, dmag = torch.empty(depth, T1, device=dev), torch.empty(T1, device=dev)
+            G.d_sd, G.d_mag_rows, G.d_mag = _ptrs(fac), rows.data_ptr(), dmag.data_ptr()
+            out["sd"] = fac + [dmag[i:i + 1] for i in range(T1)]
+        if "ab" in want:
+            r, need = self.lora_rank, _lib.lib().clhip_lora_grad_ab_ws_bytes(B * (n_prompt + 1 + self.patch_embed.num_patches), D)
+            if s.ab_grads is None or s.ab_grads.device != dev:
+                s.ab_grads = torch.empty(depth, 4 * r * D, device=dev)
+            if s.ab_ws is None or s.ab_ws.device != dev or s.ab_ws.numel() < need:
+                s.ab_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            out["ab"] = _layer_views(s.ab_grads, [(r, D), (D, r)] * 2)
+            G.d_ab, G.ab_ws = _ptrs(out["ab"]), s.ab_ws.data_ptr()
+        if prefix_lp is not None:
+            for k in ("dpk", "dpv"):
+                out[k] = [torch.empty(B, n, D, device=dev) if n else None for n in prefix_lp]
+                setattr(G, k, _ptrs(out[k]))
+        call("clhip_vit_backward", s.handle, C.byref(s.cparams), s.shadow.data_ptr(), s.ws.data_ptr(), dfeat.data_ptr(), C.byref(G), _st())
+        return out
 
     def coda_features(self, images, pool, train=False):
         """ViTZoo.forward with a CODA-Prompt pool (vit.py:120-127): [B, D] fp32, the final-LN output at the cls token of the forward whose blocks
@@ -851,13 +799,13 @@ class VisionTransformer(nn.Module):
                 raise NotImplementedError("SD-LoRA runs without prompt tokens and without the input Gram")
             params = self.sd_trainable()
             need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
-            return _VitSdFn.apply(self, images, need, *params)
+            return _VitFn.apply(self, images, None, None, need, ("sd",), *params)
         if self.lora_sub and any(a.apply_lora for a in self.attention_modules()):
             if prompt_tokens is not None or get_input_matrix:
                 raise NotImplementedError("LoRA-Sub trains without prompt tokens, and its Gram pass runs on W - prev without the LoRA term")
             params = [w for a in self.attention_modules() for w in (a.lora_A_k.weight, a.lora_B_k.weight, a.lora_A_v.weight, a.lora_B_v.weight)]
             need = torch.is_grad_enabled() and any(t.requires_grad for t in params)
-            return _VitAbFn.apply(self, images, need, *params)
+            return _VitFn.apply(self, images, None, None, need, ("ab",), *params)
         lora_b = []
         if self.lora_rank and any(a.apply_lora for a in self.attention_modules()):
             for a in self.attention_modules():
@@ -867,7 +815,8 @@ class VisionTransformer(nn.Module):
             adapters = []                                    # frozen adapters still run in the forward; they just are no autograd inputs
         need = torch.is_grad_enabled() and ((prompt_tokens is not None and prompt_tokens.requires_grad) or any(b.requires_grad for b in lora_b)
                                             or bool(adapters))
-        feat = _VitFn.apply(self, images, prompt_tokens, gram, need, len(lora_b), *lora_b, *adapters)
+        want = tuple(k for k, on in (("prompt", prompt_tokens is not None), ("lora_b", lora_b), ("adapter", adapters)) if on)
+        feat = _VitFn.apply(self, images, prompt_tokens, gram, need, want, *lora_b, *adapters)
         if get_input_matrix and gram_out is None:
             # the running mean over tokens (transformer.py:241-244) is taken when `cur_matrix` is read; here only the token count moves
             cnt = images.shape[0] * (self.patch_embed.num_patches + 1 + (0 if prompt_tokens is None else prompt_tokens.shape[0]))

@@ -56,7 +56,8 @@ def test_executor_prefix_mode_against_restatement(dim, dtype):
         plain0 = vt._run_forward(x.to(DEV), None, 0, None).clone()
         dk, dv = [None if t is None else t.to(DEV) for t in pk], [None if t is None else t.to(DEV) for t in pv]
         feat = vt._run_forward(x.to(DEV), None, 1, None, prefix=(LP, dk, dv)).clone()
-        dpk, dpv = vt._run_backward_prefix(dfeat.to(DEV), LP)
+        got = vt._run_backward(dfeat.to(DEV), prefix_lp=LP)
+        dpk, dpv = got["dpk"], got["dpv"]
         plain1 = vt._run_forward(x.to(DEV), None, 0, None).clone()
         torch.cuda.synchronize()
     assert torch.equal(plain0, plain1) and not torch.equal(plain0, feat)               # the mode switched off again: bit for bit the plain forward
@@ -81,10 +82,10 @@ def test_plain_backward_refuses_a_prefixed_forward_and_vice_versa():
     with torch.no_grad():
         vt._run_forward(x, None, 1, None, prefix=(LP, pre, pre))
         with pytest.raises(ClhipError):
-            vt._run_backward(torch.zeros(2, 64, device=DEV), False, False)
+            vt._run_backward(torch.zeros(2, 64, device=DEV))
         vt._run_forward(x, None, 1, None)
         with pytest.raises(ClhipError):
-            vt._run_backward_prefix(torch.zeros(2, 64, device=DEV), LP)
+            vt._run_backward(torch.zeros(2, 64, device=DEV), prefix_lp=LP)
 
 
 # --------------------------------------------------------------------------------------------------------------- method

@@ -59,7 +59,8 @@ def test_executor_with_mixed_prefix_lengths(lp, dim, dtype):
         plain0 = vt._run_forward(x.to(DEV), None, 0, None).clone()
         dk, dv = [None if t is None else t.to(DEV) for t in pk], [None if t is None else t.to(DEV) for t in pv]
         feat = vt._run_forward(x.to(DEV), None, 1, None, prefix=(lp, dk, dv)).clone()
-        dpk, dpv = vt._run_backward_prefix(dfeat.to(DEV), lp)
+        got = vt._run_backward(dfeat.to(DEV), prefix_lp=lp)
+        dpk, dpv = got["dpk"], got["dpv"]
         plain1 = vt._run_forward(x.to(DEV), None, 0, None).clone()
         torch.cuda.synchronize()
     assert torch.equal(plain0, plain1) and not torch.equal(plain0, feat)               # the mode switched off again: bit for bit the plain forward

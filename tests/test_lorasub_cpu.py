@@ -231,7 +231,7 @@ def test_c_abi_symbols_are_declared_and_bound():
     from libcontinual_amd import _lib
     declared = _lib.header_symbols()
     for n in ("clhip_atl", "clhip_atl_ws_bytes", "clhip_lora_grad_ab", "clhip_lora_grad_ab_ws_bytes", "clhip_proj_adam_multi", "clhip_vit_lora_refresh_ab",
-              "clhip_vit_backward_lora_ab"):
+              "clhip_vit_backward"):
         assert n in declared and n in _lib._PROTOS
         assert hasattr(_lib.lib(), n)
     with open(os.path.join(ROOT, "include", "clhip.h")) as f:

@@ -59,9 +59,9 @@ def autograd_step(c, P, X, gram0):
     for l, L in enumerate(P["layers"]):
         Wq = dd(L["qkv_w"])
         if c["lora_rank"]:
-            bk, bv = leaf(L["lora_b_k"]), leaf(L["lora_b_v"])
-            T["lora"].append((bk, bv))
-            Wq = torch.cat([Wq[:D], Wq[D:2 * D] + bk @ dd(L["lora_a_k"]), Wq[2 * D:] + bv @ dd(L["lora_a_v"])])
+            ak, bk, av, bv = [leaf(L[k]) for k in ("lora_a_k", "lora_b_k", "lora_a_v", "lora_b_v")]
+            T["lora"].append((ak, bk, av, bv))
+            Wq = torch.cat([Wq[:D], Wq[D:2 * D] + bk @ ak, Wq[2 * D:] + bv @ av])
         if c["sd"]:
             last = [leaf(L["sd"][k][-1]) for k in range(4)]                                   # A_q, B_q, A_v, B_v of the current term
             T["sd"].append(last)
@@ -134,7 +134,8 @@ def autograd_step(c, P, X, gram0):
         tap[(l, "dqin")], tap[(l, "g_ln1")] = n["h1"].grad, x[l].grad
     R["tap"] = tap
     R["d_lora_b0"] = [(torch.zeros(D, VP.LORA_RANK, dtype=torch.float64),) * 2] * depth
-    R["d_lora_b"] = [tuple(t.grad for t in T["lora"][l]) if w["lora"] else None for l in range(depth)]
+    R["d_lora_b"] = [tuple(t.grad for t in T["lora"][l][1::2]) if w["lora"] else None for l in range(depth)]
+    R["d_ab"] = [tuple(t.grad for t in T["lora"][l]) if w["ab"] else None for l in range(depth)]
     R["d_adapter"] = [tuple(t.grad for t in T["ad"][l]) if w["adapter"] else None for l in range(depth)]
     R["d_sd"] = [tuple(t.grad for t in T["sd"][l]) if w["sd"] else None for l in range(depth)]
     R["dpk"] = [T["pk"][l].grad if (w["prefix"] and T["pk"][l] is not None and l >= lowest) else None for l in range(depth)]
@@ -202,7 +203,7 @@ def test_seeded_fault_is_caught_at_its_link(fault, dt):
 
 
 @pytest.mark.parametrize("geo,mode,B,npr,lowest", [("t64", "prefix", 3, 0, 1), ("t64", "prefix_prompt", 5, 4, 0), ("t64", "lora", 3, 0, 0), ("d1", "prefix", 3, 0, 0),
-                                                   ("d1", "lora", 5, 4, 0), ("t64", "adapter", 5, 4, 0)])
+                                                   ("d1", "lora", 5, 4, 0), ("t64", "adapter", 5, 4, 0), ("t64", "lora_ab", 3, 0, 0)])
 def test_tap_slot_map_and_written_rule(geo, mode, B, npr, lowest):
     c, P = _setup(geo, mode)
     assert VP.lowest_layer(c, npr) == lowest
@@ -239,7 +240,10 @@ def test_workspace_totals_are_the_recorded_ones():
                 assert lib.clhip_vit_set_sdlora(h, len(VP.SD_RANKS), (C.c_int * len(VP.SD_RANKS))(*VP.SD_RANKS), dummy, dummy, dummy) == 0
             for B, npr in VP.batches_of(mode):
                 for flags in (1, 2, 3):
-                    assert lib.clhip_vit_workspace_bytes(h, B, npr, flags) == VP.WS_TOTALS[f"{geo}-{mode}-{dt}-b{B}-p{npr}-f{flags}"]
+                    key = f"{geo}-{mode}-{dt}-b{B}-p{npr}-f{flags}"
+                    assert lib.clhip_vit_workspace_bytes(h, B, npr, flags) == VP.WS_TOTALS[key]
+                    if mode == "lora_ab":                  # the layout depends on the descriptor alone, and that is the LoRA case's
+                        assert VP.WS_TOTALS[key] == VP.WS_TOTALS[key.replace("lora_ab", "lora")]
                     seen += 1
             assert lib.clhip_vit_tap_floats(h) == 0        # no saved forward yet
             lib.clhip_vit_destroy(h)

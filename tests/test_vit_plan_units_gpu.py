@@ -6,7 +6,8 @@ route switches are cached at their first use): every form runs in a fresh child 
 Children run one at a time, each under its own timeout; after one that timed out or ended abnormally no other child is started.  The module prints one
 `[measure]` line per form at its end (pytest -s); profiles/vit_units.md holds the table of an MI355X run.
 
-No leaf kernel sums with atomics (clhip_lora_grad, clhip_sdlora_grad, clhip_adapter_wgrad and the prefix attention backward reduce slab partials in order), so
+No leaf kernel sums with atomics (clhip_lora_grad, clhip_sdlora_grad, clhip_lora_grad_ab, clhip_adapter_wgrad and the prefix attention backward reduce slab
+partials in order), so
 the two-stream and the one-stream backward must agree bitwise on every tap and every parameter gradient, and so must the captured backward and the eager one."""
 import json
 import os
@@ -26,12 +27,14 @@ MEASURE, RESULTS = {}, {}
 _STATE = {"abnormal": None}
 
 ALL = [VP.case_id(c) for c in VP.CASES]
-LEAVES = ["t64-lora", "t64-sdlora", "t128-lora", "t128-sdlora", "d1-lora"]          # the modes whose leaves may run on the side stream
-SIDE_MODES = ("lora", "sdlora")
+# the modes whose leaves may run on the side stream; the first CAPTURED of them also run under stream capture
+LEAVES = ["t64-lora", "t64-sdlora", "t128-lora", "t128-sdlora", "t64-lora_ab", "t128-lora_ab", "d1-lora"]
+CAPTURED = 6
+SIDE_MODES = ("lora", "sdlora", "lora_ab")
 
 
 def _form(name, env, dt, cases, capture=False, side="default", routes=None):
-    """side: 'default' = the side stream exactly in the LoRA and SD-LoRA cases, 'never'; routes: the GEMM family every bf16 GEMM of the cases must take"""
+    """side: 'default' = the side stream exactly in the LoRA, SD-LoRA and LoRA-Sub cases, 'never'; routes: the GEMM family every bf16 GEMM of the cases must take"""
     return dict(name=name, env=env, dt=dt, cases=cases, capture=capture, side=side, routes=routes)
 
 
@@ -42,8 +45,8 @@ FORMS = [
     _form("WGRAD_STREAM=0-f32", dict(WGRAD_STREAM="0"), "f32", LEAVES, side="never"),
     # (fp32 attention is the generic kernel in every form: the switch only moves the bf16 head-dim-64 calls)
     _form("ATTN_GENERIC=1-bf16", dict(ATTN_GENERIC="1"), "bf16", ["t128-lora", "t128-prefix", "t128-prefix_prompt"]),
-    _form("capture-bf16", {}, "bf16", LEAVES[:4], capture=True, side="never"),
-    _form("capture-f32", {}, "f32", LEAVES[:4], capture=True, side="never"),
+    _form("capture-bf16", {}, "bf16", LEAVES[:CAPTURED], capture=True, side="never"),
+    _form("capture-f32", {}, "f32", LEAVES[:CAPTURED], capture=True, side="never"),
     # the GEMM route switches that move these shapes (all of them take the 64 x 64 tiles by default; fp32 has one kernel): GEMM_MT forces the tile
     _form("GEMM_MT=4-bf16", dict(GEMM_MT="4"), "bf16", ["t64-lora", "t128-adapter"], routes=G.T128),
     _form("GEMM_MT=5-bf16", dict(GEMM_MT="5"), "bf16", ["t64-lora"], routes=G.T160),
@@ -92,7 +95,7 @@ def test_form_launch_by_launch_against_fp64(form):
         mode = c.split("-", 1)[1]
         need = dict(lora={"h1", "d_lora_b k", "d_lora_b v"}, prompt={"dprompt", "dqin", "g_ln1"}, adapter={"ad_hd", "ad_dh", "ad_gx", "d_adapter dWd", "d_adapter dbu"},
                     adapter_drop={"ad_hd", "ad_dh", "ad_gx", "d_adapter dWu", "d_adapter dbd"}, sdlora={"h1", "d_sd dAq", "d_sd dBv", "d_sd dmag row", "d_mag"},
-                    prefix={"dpk", "dpv"}, prefix_prompt={"dpk", "dpv", "dprompt"})[mode]
+                    prefix={"dpk", "dpv"}, prefix_prompt={"dpk", "dpv", "dprompt"}, lora_ab={"h1", "d_ab dAk", "d_ab dBk", "d_ab dAv", "d_ab dBv"})[mode]
         assert need <= links, (c, sorted(need - links))
         for s, d in info[c].items():
             want_side = 1 if (form["side"] == "default" and mode in SIDE_MODES) else 0
@@ -109,7 +112,7 @@ def test_form_launch_by_launch_against_fp64(form):
 
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_two_streams_and_one_stream_agree_bitwise(dt):
-    """every tap and every parameter gradient of the LoRA / SD-LoRA cases: the side stream changes the order of launches, never a bit of a result"""
+    """every tap and every parameter gradient of the LoRA / SD-LoRA / LoRA-Sub cases: the side stream changes the order of launches, never a bit of a result"""
     two, one = RESULTS.get(f"default-{dt}"), RESULTS.get(f"WGRAD_STREAM=0-{dt}")
     assert two is not None and one is not None, "the forms this comparison needs did not run"
     for c in LEAVES:
@@ -121,5 +124,5 @@ def test_captured_backward_equals_the_eager_one_stream_backward(dt):
     """the backward under stream capture (single stream, no fork / join) and one replay against the eager WGRAD_STREAM=0 run"""
     cap, one = RESULTS.get(f"capture-{dt}"), RESULTS.get(f"WGRAD_STREAM=0-{dt}")
     assert cap is not None and one is not None, "the forms this comparison needs did not run"
-    for c in LEAVES[:4]:
+    for c in LEAVES[:CAPTURED]:
         assert cap[c] == one[c], (c, cap[c], one[c])

@@ -1,4 +1,4 @@
-"""Teacher-forced fp64 reference of the ViT executor (csrc/vit_plan.hip: clhip_vit_forward, clhip_vit_backward*) -- a helper module, not a conftest; what
+"""Teacher-forced fp64 reference of the ViT executor (csrc/vit_plan.hip: clhip_vit_forward, clhip_vit_backward) -- a helper module, not a conftest; what
 tests/plan_ref.py is for the ResNet plan.  Plain torch fp64 on the CPU; the project is not imported.
 
 The idea.  The executor keeps every link of  images -> patches -> tokens -> depth x [LN1 -> qkv -> attention -> proj(+res) -> LN2 -> fc1(GELU) -> fc2(+res)
@@ -7,7 +7,7 @@ all of them (a dict, see `emulate` for its keys; everything in it is already in 
 EXECUTOR'S OWN STORED INPUTS of that launch, with an allowed error per element.  A wiring fault -- a stale h1 at the LoRA gradient, LN2's statistics at LN1's
 backward, a lost += of a residual gradient, a g / g2 swap too many, a break one layer too high, a leaf that reads dqkv too late -- then breaks exactly one
 link by far more than a rounding bound instead of hiding in an end-to-end tolerance.  References and bounds are those of the modules that already hold each
-kernel alone (gemm_ref, vit_refs, adapter_ref, sdlora_ref, coda_ref); nothing is fitted to a kernel's output; a verdict is max over the elements of
+kernel alone (gemm_ref, vit_refs, adapter_ref, sdlora_ref, lorasub_ref, coda_ref); nothing is fitted to a kernel's output; a verdict is max over the elements of
 err / bound <= 1.
 
 Unseen tensors.  Two forward tensors are scratch and cannot be read: the LN2 output and the GELU output (and h1 where it aliases the LN2 scratch).  Their
@@ -26,6 +26,7 @@ import torch
 import adapter_ref as AR
 import coda_ref as CR
 import gemm_ref as G
+import lorasub_ref as LR
 import sdlora_ref as SR
 import vit_refs as VR
 from plan_ref import Verdict
@@ -38,7 +39,7 @@ GEOS = {
     "d1": dict(img=32, patch=8, dim=64, heads=2, mlp=256, depth=1),        # the per-layer Gram path; a backward that breaks in its first iteration
 }
 BATCHES = [(3, 0), (5, 4)]                                                 # (batch, prompt tokens): N = 17, M = 51 and N = 21, M = 105
-MODES = ["lora", "prompt", "adapter", "adapter_drop", "sdlora", "prefix", "prefix_prompt"]
+MODES = ["lora", "prompt", "adapter", "adapter_drop", "sdlora", "prefix", "prefix_prompt", "lora_ab"]        # lora_ab: LoRA-Sub, A and B both train
 CASES = [(g, m) for g in ("t64", "t128") for m in MODES] + [("d1", "lora"), ("d1", "prefix")]
 LORA_RANK, ADAPTER_DIM, ADAPTER_SCALE, DROP_P, SD_RANKS, BLOCK_EPS = 4, 16, 0.1, 0.1, (4, 6), 1e-5
 PREFIX_LP = {3: [0, 3, 8], 1: [3]}                                         # Lp[0] == 0 at depth 3: the prefix-only backward stops at layer 1
@@ -67,7 +68,7 @@ def case_id(c):
 
 
 def mode_cfg(geo, mode):
-    c = dict(GEOS[geo], lora_rank=LORA_RANK if mode == "lora" else 0, adapter_dim=ADAPTER_DIM if mode.startswith("adapter") else 0,
+    c = dict(GEOS[geo], lora_rank=LORA_RANK if mode in ("lora", "lora_ab") else 0, adapter_dim=ADAPTER_DIM if mode.startswith("adapter") else 0,
              p=DROP_P if mode == "adapter_drop" else 0.0, sd=mode == "sdlora", prefix=mode.startswith("prefix"), mode=mode)
     c["np"] = (c["img"] // c["patch"]) ** 2
     c["Kp"] = 3 * c["patch"] ** 2
@@ -83,12 +84,12 @@ def batches_of(mode):
 def wants(c, n_prompt):
     """which parameter gradients a step of this mode asks for"""
     m = c["mode"]
-    return dict(dprompt=n_prompt > 0 and m != "prefix", lora=m == "lora", adapter=c["adapter_dim"] > 0, sd=c["sd"], prefix=c["prefix"])
+    return dict(dprompt=n_prompt > 0 and m != "prefix", lora=m == "lora", adapter=c["adapter_dim"] > 0, sd=c["sd"], prefix=c["prefix"], ab=m == "lora_ab")
 
 
 def lowest_layer(c, n_prompt):
     w = wants(c, n_prompt)
-    if w["prefix"] and not (w["dprompt"] or w["lora"] or w["adapter"] or w["sd"]):
+    if w["prefix"] and not (w["dprompt"] or w["lora"] or w["adapter"] or w["sd"] or w["ab"]):
         return next(l for l, lp in enumerate(c["Lp"]) if lp > 0)
     return 0
 
@@ -229,7 +230,7 @@ def emulate(c, P, X, dt, fault=None, gram0=None, grads0=None):
       patches, pe_out, x[l] (depth + 1 entries), h1[l] (None where it aliases scratch), st1[l] / st2[l] [2, M], qkv[l], lse[l] [B, H, N], attn_o[l], x_mid[l],
       hpre[l], ad_hd[l], feat; gram0 / gram [depth, D, D] (None: no Gram pass); tap {(layer, slot): tensor} of the slots the backward wrote;
       dprompt, d_lora_b[l] = (dBk, dBv) and d_lora_b0 (the value accumulated onto), d_adapter[l] = (dWd, dbd, dWu, dbu), d_sd[l] = (dAq, dBq, dAv, dBv),
-      d_mag_rows, d_mag, dpk[l], dpv[l]; mask[l]; lowest.
+      d_ab[l] = (dAk, dBk, dAv, dBv), d_mag_rows, d_mag, dpk[l], dpv[l]; mask[l]; lowest.
     `fault` seeds ONE wiring fault (FAULTS) at layer FAULT_LAYER."""
     B, n_prompt = X["B"], X["n_prompt"]
     D, Hh, H, depth, eps = c["dim"], c["heads"], c["mlp"], c["depth"], BLOCK_EPS
@@ -290,7 +291,7 @@ def emulate(c, P, X, dt, fault=None, gram0=None, grads0=None):
     g = tap[(-1, "g0")]
     grads0 = grads0 or {}
     R["d_lora_b0"] = grads0.get("d_lora_b", [(torch.zeros(D, LORA_RANK, dtype=torch.float64),) * 2] * depth)
-    for k in ("d_lora_b", "d_adapter", "d_sd", "dpk", "dpv"):
+    for k in ("d_lora_b", "d_adapter", "d_sd", "d_ab", "dpk", "dpv"):
         R[k] = [None] * depth
     dq_of = [None] * depth
     for l in range(depth - 1, stop - 1, -1):
@@ -336,6 +337,8 @@ def emulate(c, P, X, dt, fault=None, gram0=None, grads0=None):
             want, _ = SR.grads_bounded(h1, dqkv, L["sd"], P["sd_mag"], L["sd_inv"], qq, 0.0)
             R["d_sd"][l] = tuple(f32(t) for t in want[:4])
             R.setdefault("d_mag_rows", torch.zeros(depth, len(SD_RANKS), dtype=torch.float64))[l] = f32(want[4])
+        if w["ab"]:
+            R["d_ab"][l] = tuple(f32(t) for t in LR.grads_ab(h1, dqkv, *[qq(L[k].double()) for k in ("lora_a_k", "lora_b_k", "lora_a_v", "lora_b_v")]))
     if w["sd"]:
         R["d_mag"] = f32(R["d_mag_rows"].sum(0))
     R["dprompt"] = f32(VR.prompt_grad_ref(g, B, N, n_prompt, D)) if w["dprompt"] else None
@@ -494,6 +497,11 @@ def judge(c, P, R, batched_gram=None):
             want, bound = SR.grads_bounded(R["h1"][l], tap[(l, "dqkv")], L["sd"], P["sd_mag"], L["sd_inv"], (lambda t: q(t.double(), R["dt"])), v16)
             for nm, got_, rf, bd_ in zip(("dAq", "dBq", "dAv", "dBv", "dmag row"), list(R["d_sd"][l]) + [R["d_mag_rows"][l]], want, bound):
                 V_.add(l, "d_sd " + nm, got_, rf, bd_)
+        if w["ab"]:                                                      # clhip_lora_grad_ab's own reference and bound (tests/test_lorasub_kernels_gpu.py)
+            host = [L[k] for k in ("lora_a_k", "lora_b_k", "lora_a_v", "lora_b_v")]
+            want, bound = LR.grads_ab_bounded(R["h1"][l], tap[(l, "dqkv")], host, (lambda t: q(t.double(), R["dt"])), v16)
+            for nm, got_, rf, bd_ in zip(("dAk", "dBk", "dAv", "dBv"), R["d_ab"][l], want, bound):
+                V_.add(l, "d_ab " + nm, got_, rf, bd_)
         if l == lowest and not w["dprompt"]:
             break
         if (l, "dqin") not in tap or (l, "g_ln1") not in tap:             # (reported above as "not written")

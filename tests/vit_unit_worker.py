@@ -6,7 +6,8 @@ The C API is driven through _lib directly, so the layouts and flags are this fil
   Gram buffer of zeros; then a non-saving forward with the same, now non-zero, Gram buffer (the ping-pong layout and the contiguous h1 region): its feat must be
   bitwise the saving forward's and the Gram is judged as an accumulation.
 Every step allocates exactly clhip_vit_workspace_bytes (asserted equal to the parent commit's recorded total) plus a 4 KB guard, fills workspace, guard, tap and
-every output the kernels are documented to overwrite with 0xFF bytes (NaN in both types), the accumulated lora_B gradients with a known value, reads every stored
+every output the kernels are documented to overwrite (the LoRA-Sub factor gradients and their scratch among them) with 0xFF bytes (NaN in both types), the
+accumulated lora_B gradients with a known value, reads every stored
 tensor once and judges it with vit_plan_ref.judge.  With `capture` the backward runs under torch.cuda.graph capture and one replay.  After step 0 the refusals
 are tried: each must return an error, set clhip_last_error and launch nothing.
 Prints `RATIOS {case: {"s<step> <link>": worst err / bound}}`, `INFO {case: {...}}`, `BITS {case: {"s<step>": sha1 of the tap and of the parameter gradients}}`,
@@ -53,6 +54,15 @@ def nan_f32(*shape):
 
 def ptrs(ts):
     return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def grads(**members):
+    """a clhip_vit_grads: a tensor gives its pointer, a list of tensors a pointer table (kept alive by the structure), None stays NULL"""
+    g = _lib.VitGrads()
+    for k, v in members.items():
+        if v is not None:
+            setattr(g, k, ptrs(v) if isinstance(v, list) else v.data_ptr())
+    return g
 
 
 def cpu64(t):
@@ -193,18 +203,16 @@ def run_case(geo, mode, dt, capture):
         d_rows, d_mag = (nan_f32(depth, len(VP.SD_RANKS)), nan_f32(len(VP.SD_RANKS))) if w["sd"] else (None, None)
         dpk = [None if not lp else nan_f32(B * lp, D) for lp in c["Lp"]] if w["prefix"] else None
         dpv = [None if not lp else nan_f32(B * lp, D) for lp in c["Lp"]] if w["prefix"] else None
+        rk = VP.LORA_RANK
+        d_ab = [nan_f32(*s) for _ in range(depth) for s in ((rk, D), (D, rk), (rk, D), (D, rk))] if w["ab"] else None      # written, not accumulated into
+        ab_ws = torch.full((lib.clhip_lora_grad_ab_ws_bytes(M, D),), 0xFF, dtype=torch.uint8, device=DEV) if w["ab"] else None
         lora0 = [cpu64(t) for t in lora_acc] if w["lora"] else None
-        common = (h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), dfeat.data_ptr(), dprompt.data_ptr() if w["dprompt"] else None)
+        common = (h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), dfeat.data_ptr())
+        G = grads(dprompt_tokens=dprompt, d_lora_b=lora_acc if w["lora"] else None, d_adapter=d_ad, d_sd=d_sd, d_mag_rows=d_rows, d_mag=d_mag, d_ab=d_ab, ab_ws=ab_ws,
+                  dpk=dpk, dpv=dpv)
 
         def backward(stream):
-            if w["adapter"]:
-                call("clhip_vit_backward_adapter", *common, None, ptrs(d_ad), stream)
-            elif w["sd"]:
-                call("clhip_vit_backward_sdlora", *common, ptrs(d_sd), d_rows.data_ptr(), d_mag.data_ptr(), stream)
-            elif w["prefix"]:
-                call("clhip_vit_backward_prefix", *common, None, ptrs(dpk), ptrs(dpv), stream)
-            else:
-                call("clhip_vit_backward", *common, ptrs(lora_acc) if w["lora"] else None, stream)
+            call("clhip_vit_backward", *common, C.byref(G), stream)
         if capture:
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
@@ -252,6 +260,7 @@ def run_case(geo, mode, dt, capture):
         R["d_lora_b"] = [(cpu64(lora_acc[2 * l]), cpu64(lora_acc[2 * l + 1])) if w["lora"] else None for l in range(depth)]
         R["d_adapter"] = [tuple(cpu64(t) for t in d_ad[4 * l:4 * l + 4]) if w["adapter"] else None for l in range(depth)]
         R["d_sd"] = [tuple(cpu64(t) for t in d_sd[4 * l:4 * l + 4]) if w["sd"] else None for l in range(depth)]
+        R["d_ab"] = [tuple(cpu64(t) for t in d_ab[4 * l:4 * l + 4]) if w["ab"] else None for l in range(depth)]
         if w["sd"]:
             R["d_mag_rows"], R["d_mag"] = cpu64(d_rows), cpu64(d_mag)
         R["dpk"] = [cpu64(t) if (t is not None and l >= low.value) else None for l, t in enumerate(dpk)] if w["prefix"] else [None] * depth
@@ -264,7 +273,7 @@ def run_case(geo, mode, dt, capture):
             ratios[f"s{i} {k}"] = v
         for k, v in V.failures().items():
             print(f"FAIL {geo}-{mode} step {i} {k}: {v:.4g}", flush=True)
-        leaves = [t for ts in (lora_acc if w["lora"] else None, d_ad, d_sd, [d_rows, d_mag] if w["sd"] else None, dpk, dpv, [dprompt]) if ts for t in ts if t is not None]
+        leaves = [t for ts in (lora_acc if w["lora"] else None, d_ad, d_sd, [d_rows, d_mag] if w["sd"] else None, d_ab, dpk, dpv, [dprompt]) if ts for t in ts if t is not None]
         sha = lambda ts: hashlib.sha1(b"".join(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes() for t in ts)).hexdigest()
         bits[f"s{i}"] = dict(tap=sha([tapbuf]), leaves=sha(leaves) if leaves else "")
         call("clhip_vit_set_tap", h, None, 0)
@@ -273,7 +282,7 @@ def run_case(geo, mode, dt, capture):
         if mode == "prefix" and npr > 0:
             # the same saved forward again, now with the prompt gradient: the chain runs to layer 0 and the prefix gradients of the layers above stay bitwise
             dp2, dpk2, dpv2 = nan_f32(npr, D), [None if t is None else nan_f32(*t.shape) for t in dpk], [None if t is None else nan_f32(*t.shape) for t in dpv]
-            call("clhip_vit_backward_prefix", h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), dfeat.data_ptr(), dp2.data_ptr(), None, ptrs(dpk2), ptrs(dpv2), st())
+            call("clhip_vit_backward", *common, C.byref(grads(dprompt_tokens=dp2, dpk=dpk2, dpv=dpv2)), st())
             torch.cuda.synchronize()
             call("clhip_vit_last_backward_info", h, C.byref(side), C.byref(low))
             assert low.value == 0 and info[f"s{i}"]["lowest"] == (1 if depth > 1 else 0)
@@ -306,7 +315,7 @@ def run_case(geo, mode, dt, capture):
         print(f"FAIL {geo}-{mode} non-saving forward gram: {worst:.4g}", flush=True)
     out = nan_f32(M1, D)
     refused("clhip_vit_read_act", [out], h, ws.data_ptr(), 0, 0, out.data_ptr(), st())                       # x_in is one of two ping-pong buffers there
-    refused("clhip_vit_backward", [out], h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), out.data_ptr(), None, None, st())     # a backward after a non-saving forward
+    refused("clhip_vit_backward", [out], h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), out.data_ptr(), None, st())           # a backward after a non-saving forward
     lib.clhip_vit_destroy(h)
     return ratios, info, bits
 
@@ -323,24 +332,35 @@ def refusals(ex, c, ws, X, dfeat, B, npr, own_h1, pk, pv):
     if not c["adapter_dim"]:
         refused("clhip_vit_read_act", [out], h, ws.data_ptr(), 0, 9, out.data_ptr(), st())
         d_ad = [nan_f32(D, 16) for _ in range(4 * depth)]
-        refused("clhip_vit_backward_adapter", d_ad, *base, None, None, ptrs(d_ad), st())                 # d_adapter on an executor without adapters
+        refused("clhip_vit_backward", d_ad, *base, C.byref(grads(d_adapter=d_ad)), st())                  # d_adapter on an executor without adapters
     if npr == 0:
-        refused("clhip_vit_backward", [out], *base, out.data_ptr(), None, st())                           # dprompt when n_prompt == 0
+        refused("clhip_vit_backward", [out], *base, C.byref(grads(dprompt_tokens=out)), st())             # dprompt when n_prompt == 0
     if c["prefix"]:
-        refused("clhip_vit_backward", [out], *base, None, None, st())                                     # dpk missing after a prefixed forward
+        refused("clhip_vit_backward", [out], *base, None, st())                                           # dpk missing after a prefixed forward
+        refused("clhip_vit_backward", big, *base, C.byref(grads(dpk=big)), st())                          # dpk without dpv
     else:
-        refused("clhip_vit_backward_prefix", big, *base, None, None, ptrs(big), ptrs(big), st())          # dpk given after a plain forward
+        refused("clhip_vit_backward", big, *base, C.byref(grads(dpk=big, dpv=big)), st())                 # dpk given after a plain forward
+    if c["lora_rank"]:
+        rk = c["lora_rank"]
+        d_ab = [nan_f32(*s) for _ in range(depth) for s in ((rk, D), (D, rk), (rk, D), (D, rk))]
+        d_b = [nan_f32(D, rk) for _ in range(2 * depth)]
+        ab_ws = torch.full((_lib.lib().clhip_lora_grad_ab_ws_bytes(M, D),), 0xFF, dtype=torch.uint8, device=DEV)
+        refused("clhip_vit_backward", d_ab + d_b + [ab_ws], *base, C.byref(grads(d_ab=d_ab, ab_ws=ab_ws, d_lora_b=d_b)), st())     # d_ab together with d_lora_b
+        refused("clhip_vit_backward", d_ab, *base, C.byref(grads(d_ab=d_ab)), st())                       # d_ab without ab_ws
     feat = nan_f32(B, D)
     n_big = 256 - c["np"]                                                                                 # n_prompt + 1 + np = 257 tokens
     assert _lib.lib().clhip_vit_workspace_bytes(h, B, n_big, 1) == 0
     refused("clhip_vit_forward", [feat], h, C.byref(ex.params), ex.shadow.data_ptr(), ws.data_ptr(), X["img"].to(DEV).data_ptr(), B, ex.prompt.data_ptr(), n_big, 1,
             None, feat.data_ptr(), st())
-    if c["sd"]:                                                                                           # a backward after clhip_vit_set_sdlora changed the term set
-        ex.set_sdlora()
+    if c["sd"]:
         rT, T = VP.SD_RANKS[-1], len(VP.SD_RANKS)
         d_sd = [nan_f32(*s) for _ in range(depth) for s in ((rT, D), (D, rT), (rT, D), (D, rT))]
         rows, mag = nan_f32(depth, T), nan_f32(T)
-        refused("clhip_vit_backward_sdlora", d_sd + [rows, mag], *base, None, ptrs(d_sd), rows.data_ptr(), mag.data_ptr(), st())
+        d_b = [nan_f32(D, rT) for _ in range(2 * depth)]
+        refused("clhip_vit_backward", d_sd + d_b + [rows, mag], *base, C.byref(grads(d_sd=d_sd, d_mag_rows=rows, d_mag=mag, d_lora_b=d_b)), st())   # d_sd together with d_lora_b
+        refused("clhip_vit_backward", d_sd + [rows], *base, C.byref(grads(d_sd=d_sd, d_mag_rows=rows)), st())                                       # d_sd without d_mag
+        ex.set_sdlora()                                                                                   # a backward after clhip_vit_set_sdlora changed the term set
+        refused("clhip_vit_backward", d_sd + [rows, mag], *base, C.byref(grads(d_sd=d_sd, d_mag_rows=rows, d_mag=mag)), st())
 
 
 def gemm_routes(c, dt):

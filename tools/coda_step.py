@@ -96,8 +96,9 @@ def coda(batch, reps, inner):
         pk, pv = [e[0, i] if i < 5 else None for i in range(12)], [e[1, i] if i < 5 else None for i in range(12)]
         res["prefixed_forward_ms"] = timed(lambda: vt._run_forward(x, None, 1, None, prefix=(lp, pk, pv)), reps, inner)
         dfeat = torch.randn(batch, D, device=DEV)
-        res["backward_ms"] = timed(lambda: vt._run_backward_prefix(dfeat, lp), reps, inner)
-        dpk, dpv = vt._run_backward_prefix(dfeat, lp)
+        res["backward_ms"] = timed(lambda: vt._run_backward(dfeat, prefix_lp=lp), reps, inner)
+        g = vt._run_backward(dfeat, prefix_lp=lp)
+        dpk, dpv = g["dpk"], g["dpv"]
         grads = [torch.zeros_like(t) for t in params]
         ws = torch.empty(_lib.lib().clhip_coda_ws_bytes(n, batch, 0, f) // 4, device=DEV)
         bwd = lambda: call("clhip_coda_bwd", n, q.data_ptr(), arr(params[0::3]), arr(params[1::3]), arr(params[2::3]), c.data_ptr(), arr(dpk[:5]), arr(dpv[:5]),

@@ -82,8 +82,9 @@ def dual(batch, reps, inner, task_id=3):
         pv = [pre[i][1] if i < ng + ne else None for i in range(12)]
         res["prefixed_forward_ms"] = timed(lambda: vt._run_forward(x, None, 1, None, prefix=(lp, pk, pv)), reps, inner)
         dfeat = torch.randn(batch, D, device=DEV)
-        res["backward_ms"] = timed(lambda: vt._run_backward_prefix(dfeat, lp), reps, inner)
-        dpk, dpv = vt._run_backward_prefix(dfeat, lp)
+        res["backward_ms"] = timed(lambda: vt._run_backward(dfeat, prefix_lp=lp), reps, inner)
+        g = vt._run_backward(dfeat, prefix_lp=lp)
+        dpk, dpv = g["dpk"], g["dpv"]
         grads = [torch.zeros_like(t) for t in params]
         one = torch.ones(1, device=DEV)
         bwd = lambda: call("clhip_dual_bwd", ng, ne, q.data_ptr(), arr(e_k), arr(dpk[:ng + ne]), arr(dpv[:ng + ne]), one.data_ptr(), arr(grads[:ng]),
