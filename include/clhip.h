@@ -534,6 +534,9 @@ int clhip_conv_fwd_acc_bn_input_wt(const void* z_in, const clhip_bn_input* bn /*
 #define CLHIP_CONV_WGRAD_V1 22     /* conv.hip conv_wgrad_kernel (CONV_V1), LDS transpose read in bf16 */
 #define CLHIP_CONV_WGRAD_V1_NO_TR 23 /* conv.hip conv_wgrad_kernel without the transpose read (WGRAD_NO_TR; fp32 always) */
 int clhip_conv_route(int op, int form, int N, int H, int W, int C, int Creal, int K, int ksize, int stride, int pad, int dtype);
+/* Number of launches, in this process, of the entry-block body of conv2.hip (the 3x3/s2 forwards behind ENTRY_S2).  The body stores the generic kernel's
+ * bits, so its outputs cannot tell which kernel ran: tests and A/B runs read this counter instead. */
+long long clhip_conv_entry_s2_launches(void);
 int clhip_conv_dgrad_wgrad_bn_input(const void* x_z, const float* x_coef, const void* dz, const void* w_dg, void* dx, int accumulate, float* dw,
                                     void* ws, const float* mean, const float* invstd, double* acc /*nullable*/, int replicas, int N, int H, int W,
                                     int C, int Creal, int K, int ksize, int stride, int pad, int dtype, void* stream);
@@ -583,6 +586,7 @@ int clhip_conv_wgrad_pair(const void* x, const void* dz, const void* dz_sc, floa
  * pin a code path, tools/ to sweep.
  *   dispatch (0 / 1 unless noted):
  *     CONV4 (0: 3x3/s1 layers stay on conv3.hip), CONV5 (0: the 64 -> 64-channel 3x3/s1 layers stay on conv4.hip), CONV64 (0: 64 -> 64 channels on small maps stay on conv4 / wgrad4; CONV64_FWD 0: only their backward; CONV64_BM 64 | 128), CONV6 (0: no fused stride-2 dgrad pair kernel), CONV6_PAIR (0: plans keep the two separate input-gradient launches), CONV7 (0: no small-channel entry kernels; FWD7 0 / WGRAD7 0: not their forward / weight-gradient pairs; CONV7_TPW n: tiles per wave), BN_INPUT (0: no lazy BatchNorm inputs), BN_INPUT_WT (0: not on the LDS-DMA kernels of the wide layers), BN_RES_INPUT (0: block outputs keep their own apply launch), EVAL_LAZY (0: eval-mode forwards keep one BatchNorm apply launch per unit instead of the consumer-side forms), BN_GRAD (0: no BatchNorm backward on the operand loads; BN_GRAD_MINC n: only for layers of >= n channels, BN_GRAD_RES 0: not for the +res layers), CONV_V1,
+ *     ENTRY_S2 (0: the 3x3/s2 entry forwards of 64 / 128 / 256 -> twice as many channels stay on the generic kernel of conv2.hip; read on every call),
  *     NO_CONV3, NO_CONV16, NO_STEM, NO_SHORTCUT, NO_PARITY_DGRAD, CONV3G, WGRAD4 (0 off, 2 stride-1 layers only), WGRAD5, WGRAD32,
  *     WGRAD_NO_TR, WGRAD2_ATOMIC (1: the generic weight-gradient kernel keeps fp32 atomics even when scratch is handed in), BWD_FUSED (0: dgrad and weight gradient of the 16 / 32-channel layers as two launches), WGRAD_DEFER_SIDE (n > 0: plans WITH a weight-gradient stream reduce in groups of n launches), WGRAD_DEFER (0: plans without a weight-gradient stream reduce their partial blocks per layer instead of once per backward), GEMM_NO_SPLIT, GEMM_TAIL, GEMM_SPLITK (0: no split-K for the few-tile / long-K products; n > 1: the minimum K that splits, default 3072), ATTN_GENERIC, CE_ROWS,
  *     BN_PARTIALS (partial rows + finalize launches instead of the fp64 accumulators), BN_FUSE (0 never, 1 everywhere; default: small

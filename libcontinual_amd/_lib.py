@@ -173,6 +173,7 @@ _PROTOS = {
     "clhip_gemm_nt": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 10 + [_p]),
     "clhip_gemm_nt_route": (_i, [_i] * 9 + [C.POINTER(C.c_int), _i]),
     "clhip_conv_route": (_i, [_i] * 12),
+    "clhip_conv_entry_s2_launches": (C.c_longlong, []),
     "clhip_config": (_i, [C.c_char_p, C.c_char_p]),
     "clhip_config_get": (C.c_char_p, [C.c_char_p]),
     "clhip_conv_bn_input_wt_supported": (_i, [_i] * 9),

@@ -279,6 +279,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     }
 }
 
+// eight elements as they sit in memory (bf16: four packed pairs in one uint4; fp32: two float4): what the accumulator-path apply kernels hold
+// across their prologue -- a quarter (half) of the registers of the unpacked fp32 form
+template <typename T> struct Raw8;
+template <> struct Raw8<bf16_t> { uint4 a; };
+template <> struct Raw8<float> { float4 a, b; };
+template <typename T> __device__ __forceinline__ Raw8<T> raw_load8(const T* p) {
+    Raw8<T> r;
+    if constexpr (sizeof(T) == 2) { r.a = *reinterpret_cast<const uint4*>(p); }
+    else { r.a = *reinterpret_cast<const float4*>(p); r.b = *reinterpret_cast<const float4*>(p + 4); }
+    return r;
+}
+template <typename T> __device__ __forceinline__ void raw_unpack8(const Raw8<T>& r, float (&v)[8]) {      // load8's values, bit for bit
+    if constexpr (sizeof(T) == 2) { unpack8(r.a, v); }
+    else { v[0] = r.a.x; v[1] = r.a.y; v[2] = r.a.z; v[3] = r.a.w; v[4] = r.b.x; v[5] = r.b.y; v[6] = r.b.z; v[7] = r.b.w; }
+}
+
 // ---------------------------------------------------------------------------- accumulator ("acc") variants
 // The per-layer finalize launches (bn_finalize, bn_bwd_finalize: 40 x ~6 us of a 3.3 ms ResNet-18 step) disappear when the
 // producer adds its per-channel sums into a [2][C] fp64 accumulator with hardware fp64 atomics (order-independent to ~1e-16)
@@ -291,6 +307,18 @@ __global__ __launch_bounds__(256) void bn_apply_train_kernel(const T* __restrict
                                                              const T* __restrict__ res, T* __restrict__ y, int64_t nchunks, int C,
                                                              unsigned char* __restrict__ relu_mask = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float coefs[];       // [2][C]: scale, shift
+    // UN chunks per trip, every load issued before the first use: the kernels are a few dependent round trips long on the small layers.  The
+    // first trip's operands do not depend on the coefficients: their loads go out BEFORE the prologue's accumulator loads and are held packed
+    // across its barrier, so the launch is one memory round trip to its first store instead of two (most launches make one trip per thread).
+    constexpr int UN = 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Raw8<T> pv[UN], pr[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+        const int64_t iu = i0 + u * stride;
+        if (iu < nchunks) { pv[u] = raw_load8<T>(z + iu * 8); if (RES) pr[u] = raw_load8<T>(res + iu * 8); }
+    }
     // block-cooperative finalize: sum the accumulator replicas, derive scale / shift once per workgroup
     __shared__ double sred[256];
     const bool narrow = 2 * C <= 128;
@@ -322,25 +350,25 @@ __global__ __launch_bounds__(256) void bn_apply_train_kernel(const T* __restrict
         }
     }
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int c0 = ((int)i0 & ((C >> 3) - 1)) * 8;                     // fixed per thread: C is a power of two and the grid stride a multiple of C/8
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { sc[e] = coefs[c0 + e]; sh[e] = coefs[C + c0 + e]; }
-    // UN chunks per trip, every load issued before the first use: the kernels are a few dependent round trips long on the small layers
-    constexpr int UN = 4;
     for (int64_t i = i0; i < nchunks; i += stride * UN) {
         float v[UN][8], r[UN][8];
+        if (i != i0) {                                                  // (the first trip's operands are already here)
 #pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int64_t iu = i + u * stride;
-            if (iu < nchunks) { load8<T>(z + iu * 8, v[u]); if (RES) load8<T>(res + iu * 8, r[u]); }
+            for (int u = 0; u < UN; ++u) {
+                const int64_t iu = i + u * stride;
+                if (iu < nchunks) { pv[u] = raw_load8<T>(z + iu * 8); if (RES) pr[u] = raw_load8<T>(res + iu * 8); }
+            }
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int64_t iu = i + u * stride;
             if (iu >= nchunks) break;
+            raw_unpack8<T>(pv[u], v[u]);
+            if (RES) raw_unpack8<T>(pr[u], r[u]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float o = fmaf(v[u][e], sc[e], sh[e]);
@@ -369,6 +397,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const T* __restri
     // [6][C]: mean(g), mean(g * xhat), mean, invstd, scale, shift -- every per-channel constant goes through LDS once per workgroup (32
     // four-byte gathers per thread from the four parameter arrays were most of this kernel's fixed cost on the small layers)
     extern __shared__ __attribute__((aligned(16))) float coefs[];
+    // the first trip's operand loads go out before the prologue and are held packed across its barrier (see bn_apply_train_kernel)
+    constexpr int UN = sizeof(T) == 2 ? 4 : 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Raw8<T> pg[UN], pz[UN], py[UN], pr[UN];
+    unsigned mk[UN];
+    auto issue = [&](int64_t i) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            mk[u] = 0;
+            const int64_t iu = i + u * stride;
+            if (iu < nchunks) {
+                pg[u] = raw_load8<T>(dy + iu * 8);
+                pz[u] = raw_load8<T>(z + iu * 8);
+                if (RELU == 1) py[u] = raw_load8<T>(y + iu * 8);
+                if (RELU == 3) mk[u] = reinterpret_cast<const unsigned char*>(y)[iu];
+                if (DRES == 2) pr[u] = raw_load8<T>(dres + iu * 8);
+            }
+        }
+    };
+    issue(i0);
     __shared__ double sred[256];
     const bool narrow = 2 * C <= 128;
     if (narrow) replica_parts(acc, rep, C, sred);
@@ -388,8 +437,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const T* __restri
         if (blockIdx.x == 0) { dbeta[c] = db_old + (float)s1; dgamma[c] = dg_old + (float)s2; }
     }
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int c0 = ((int)i0 & ((C >> 3) - 1)) * 8;
     float k0[8], k1[8], gi[8], mu[8], is[8], sh[8];
 #pragma unroll
@@ -401,26 +448,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const T* __restri
         gi[e] = coefs[4 * C + c0 + e];
         if (RELU == 2) sh[e] = coefs[5 * C + c0 + e];
     }
-    constexpr int UN = sizeof(T) == 2 ? 4 : 2;
     for (int64_t i = i0; i < nchunks; i += stride * UN) {
         float g[UN][8], yy[UN][8], zz[UN][8], rr[UN][8];
-        unsigned mk[UN];
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            mk[u] = 0;
-            const int64_t iu = i + u * stride;
-            if (iu < nchunks) {
-                load8<T>(dy + iu * 8, g[u]);
-                load8<T>(z + iu * 8, zz[u]);
-                if (RELU == 1) load8<T>(y + iu * 8, yy[u]);
-                if (RELU == 3) mk[u] = reinterpret_cast<const unsigned char*>(y)[iu];
-                if (DRES == 2) load8<T>(dres + iu * 8, rr[u]);
-            }
-        }
+        if (i != i0) issue(i);
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int64_t iu = i + u * stride;
             if (iu >= nchunks) break;
+            raw_unpack8<T>(pg[u], g[u]);
+            raw_unpack8<T>(pz[u], zz[u]);
+            if (RELU == 1) raw_unpack8<T>(py[u], yy[u]);
+            if (DRES == 2) raw_unpack8<T>(pr[u], rr[u]);
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
