@@ -309,6 +309,16 @@ int clhip_plan_backward_range(clhip_plan* p, const float* dfeat, const float* pa
  * (clhip_config("STAGE_TRAIN", "0") before the forward keeps the per-unit backward). */
 int clhip_plan_read_act(clhip_plan*, const void* workspace, int idx, int which, float* out_nchw, void* stream);
 
+/* A run of nconv / 2 BasicBlocks (conv3x3 C -> C, stride 1 -> BN -> ReLU -> conv3x3 -> BN -> + block input -> ReLU) in eval mode as ONE launch, the image
+ * resident in LDS (csrc/stage.hip) -- what the eval forward of a bf16 plan makes of such a run (clhip_config("STAGE_EVAL", "0") keeps one launch per unit); the
+ * direct entry reads no switch.  x, y: [N][H][W][C] bf16 (y may not alias x); w[i]: the [C][9][C] bf16 forward copy of convolution i exactly as
+ * clhip_conv_weight_prep writes w_fwd; gamma / beta / mean / var[i]: its BatchNorm weight, bias and running statistics (fp32, C each); the five tables are host
+ * arrays of nconv device pointers.  Every pre-BatchNorm value is rounded to bf16 as the per-unit path stores it.  Supported (the query returns 1, else 0): bf16,
+ * (C, H = W) = (16, 32), (32, 16) or (64, 8), nconv even in 2 .. 16; the call also needs N >= 1.  Anything else is CLHIP_EINVAL before a launch. */
+int clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype);
+int clhip_stage_eval(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
+                     const float* const* mean, const float* const* var, float eps, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Heads and losses (fp32).
  * linear: out[B,O] = x[B,D] W[O,D]^T + b   (nn.Linear heads: ewc.py:50, lwf.py:29-40, icarl.py:31)      */

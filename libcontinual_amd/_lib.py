@@ -138,6 +138,8 @@ _PROTOS = {
     "clhip_plan_unit_forms": (_i, [_p, _i, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "clhip_plan_backward_range": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "clhip_plan_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
+    "clhip_stage_eval_supported": (_i, [_i] * 5),
+    "clhip_stage_eval": (_i, [_p, _p] + [_i] * 5 + [_p] * 5 + [_f, _i, _p]),
     "clhip_linear_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "clhip_linear_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_ce_slice": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _p, _p]),

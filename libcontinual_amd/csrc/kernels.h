@@ -146,8 +146,7 @@ int clhip_gemm8_launch(const void* A, const void* B, void* C, const float* bias,
 bool clhip_shortcut_supported(int N, int H, int W, int C, int K, int ksize, int stride, int pad, int dtype);
 int clhip_shortcut_dgrad(const void* dz, const void* w_dg, void* dx, int accumulate, int N, int H, int W, int C, int K, hipStream_t st);
 
-// ---- stage.hip
-bool clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype);
+// ---- stage.hip (its predicate clhip_stage_eval_supported is part of the C ABI: include/clhip.h)
 int clhip_stage_eval_launch(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
                             const float* const* mean, const float* const* var, float eps, int dtype, hipStream_t st);
 

@@ -217,8 +217,8 @@ int launch_stage(const StageParams& p, hipStream_t st) {
 
 }  // namespace
 
-bool clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype) {
-    if (dtype != CLHIP_BF16 || H != W || nconv < 2 || nconv > kMaxConv || (nconv & 1)) return false;
+extern "C" int clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype) {
+    if (dtype != CLHIP_BF16 || H != W || nconv < 2 || nconv > kMaxConv || (nconv & 1)) return 0;
     return (C == 16 && H == 32) || (C == 32 && H == 16) || (C == 64 && H == 8);
 }
 
@@ -234,4 +234,13 @@ int clhip_stage_eval_launch(const void* x, void* y, int N, int H, int W, int C, 
     if (C == 16) return launch_stage<16, 32>(p, st);
     if (C == 32) return launch_stage<32, 16>(p, st);
     return launch_stage<64, 8>(p, st);
+}
+
+// the C ABI of the launcher (include/clhip.h): the geometry is judged before a pointer table is read
+extern "C" int clhip_stage_eval(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
+                                const float* const* mean, const float* const* var, float eps, int dtype, void* stream) {
+    if (!clhip_stage_eval_supported(H, W, C, nconv, dtype) || N < 1) { clhip_set_error("stage_eval: unsupported geometry"); return CLHIP_EINVAL; }
+    CLHIP_CHECK_ARG(x && y && x != y && w && gamma && beta && mean && var);
+    for (int i = 0; i < nconv; ++i) CLHIP_CHECK_ARG(w[i] && gamma[i] && beta[i] && mean[i] && var[i]);
+    return clhip_stage_eval_launch(x, y, N, H, W, C, nconv, w, gamma, beta, mean, var, eps, dtype, (hipStream_t)stream);
 }

@@ -515,11 +515,14 @@ def judge(units, D, dt, pool_win, nbt=None):
     return V
 
 
-def judge_eval(units, D, dt):
+def judge_eval(units, D, dt, only=None):
     """the eval forward per unit: z from its stored input, y = relu?(z scale + shift (+ res)) of the running statistics (bound_y kind "eval": the running
-    mean is an exact fp32 input).  D: x, z, y, w, gamma, beta, rm, rv"""
+    mean is an exact fp32 input).  D: x, z, y, w, gamma, beta, rm, rv.  only: the units to judge (None: all) -- the units of a run that the eval forward took as
+    one launch (stage.hip) have no stored z and y; tests/stage_eval_worker.py holds those to the kernel itself"""
     V = Verdict()
     for i, u in enumerate(units):
+        if only is not None and i not in only:
+            continue
         ref, bound, _ = z_link(units, i, D, dt)
         V.add(i, "eval z", D["z"][i], ref, bound)
         if not has_bn(u):

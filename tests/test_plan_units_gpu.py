@@ -2,7 +2,7 @@
 tensor of a training step (z, the batch statistics, y, feat, dy of every activation, dw, dgamma, dbeta; a second pass onto the first one's gradients) and of an
 eval forward against what fp64 makes of the plan's own stored inputs of that link.  The parent process never flips a switch (most are cached at their first
 use and would leak across files): every form runs in a fresh child (tests/plan_unit_worker.py) with its switches as CLHIP_<NAME> in the environment, STAGE_TRAIN
-= 0 in all of them (the stage-level launches keep their own file; dy does not exist inside them) and STAGE_EVAL = 0 (so every eval activation is readable).
+= 0 in all of them (the stage-level launches keep their own file; dy does not exist inside them) and STAGE_EVAL = 0 (so every eval activation is readable; tests/test_stage_eval_plan_gpu.py holds the default, where runs of blocks are one launch).
 Children run one at a time; after one that timed out or ended abnormally no other child is started.  Every form asserts through clhip_plan_unit_forms that the
 units it is meant to exercise took that branch.  The module prints one `[measure]` line per form at its end (pytest -s); profiles/plan_units.md holds the table
 of an MI355X run."""
