@@ -424,7 +424,9 @@ int clhip_herding_select_batched(const float* feats, const int32_t* offsets, int
  * clhip_gemm_nt: C[M,N] = epi(A[M,K] . B[N,K]^T); replaces every F.linear on the path (transformer.py:172,194,
  *   255,1267-1271) and, with the [in,out] copy of a frozen weight as B, its input gradient.  Epilogues:
  *   0 none | 1 +bias | 2 +bias +R (residual add, :1333-1334) | 3 +bias, then C <- GELU(.) (:1268) and H <- GELU'(.)
- *   (nullable; saved for the backward) | 4 C <- (.) * H (backward of 3).  bias fp32; R, H in the compute dtype.
+ *   (nullable; saved for the backward) | 4 C <- (.) * H (backward of 3 and 6) | 6 +bias, then CLIP's QuickGELU (transformer.py:137-139): with
+ *   s = sigmoid(1.702 x), C <- x s and H <- s (1 + 1.702 x (1 - s)) (nullable; C has the same bits with and without H); one exp of -|1.702 x| gives s
+ *   and 1 - s, so no |x| overflows or forms 0 * inf.  (5 is not an epilogue: it stays CLHIP_EINVAL.)  bias fp32; R, H in the compute dtype.
  *   K % 64 == 0, N % 4 == 0, lda and ldb % 8 == 0.  Output-side pitches (ldc; ldr when R is given; ldh when H is given): % 4 == 0, and % 8 == 0 for a
  *   bf16 product with N % 8 == 0 -- its kernels move C, R and H as 16-byte chunks at row * ld + 8 c, so every row must start 16-byte aligned (bf16 with
  *   N % 8 == 4 stores 8 bytes at a time and fp32 rows of ld % 4 == 0 are 16-byte aligned: both keep % 4).  Anything else is CLHIP_EINVAL before a launch.
@@ -871,6 +873,34 @@ int clhip_vit_lora_refresh_ab(clhip_vit*, const clhip_vit_params* params, void* 
  *          switching afterwards does not disturb its backward.  The saved lse stays [B, H, N]; the workspace size does not change.
  *          Its gradients: the dpk / dpv members of clhip_vit_grads. */
 int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* const* pk, const void* const* pv);
+/* CLIP mode of the executor: the visual tower of the reference's CLIP backbone (VisualTransformer.forward, transformer.py:2121-2140) is this ViT with
+ * four differences.  Descriptors and parameter tables are untouched; a caller that never calls this gets the executor it had.
+ * set_clip: ln_pre_w / ln_pre_b [D] fp32 on the device (alive while the mode is on; both NULL = no ln_pre), final_eps = eps of the pooled final LN
+ *          (ln_post: 1e-5; the executor's own is 1e-6), quick_gelu 0 / 1.  NULL ln_pre together with quick_gelu == 0 switches the mode off (final_eps is
+ *          then ignored and 1e-6 again).  The state PERSISTS.  In the mode:
+ *            - pe_b == NULL in clhip_vit_params means a patch convolution without bias (:2107); outside the mode a NULL pe_b is refused;
+ *            - the assembled token rows (class embedding + pos[0] | patches + pos[1..], :2125-2126) are normalised by ln_pre (eps 1e-5, :2127): layer 0's
+ *              saved x_in (clhip_vit_read_act which 0) is the ln_pre OUTPUT.  The un-normalised rows pass through the LN scratch: no workspace change;
+ *            - fc1 runs epilogue 6 of clhip_gemm_nt (QuickGELU, :137-139); its backward is epilogue 4 on the saved derivative as before;
+ *            - clhip_ln_pool_fwd / _bwd run with final_eps (a backward uses the eps of the forward it belongs to).
+ *          block_ln_eps = 0 in the descriptor already gives the blocks' 1e-5.  The Gram accumulation and d_lora_b work unchanged.  Without prompt tokens
+ *          the backward stops at the lowest layer's attention backward, so ln_pre has no backward.
+ *          Prompt tokens, prefix mode, adapters and SD-LoRA do not combine with the mode: set_clip refuses an executor that has them, and a forward in
+ *          the mode refuses them, with CLHIP_EINVAL before any launch. */
+int clhip_vit_set_clip(clhip_vit* v, const float* ln_pre_w, const float* ln_pre_b, float final_eps, int quick_gelu);
+/* CLIP's image-side logits (CLIP.forward, core/model/backbone/clip.py:405-412; csrc/clip.hip).  Exact fp32, no atomics, every sum in a fixed order: two
+ * runs are bitwise equal.  One workgroup per image, one launch each way.
+ * fwd: feat [B, D] (the executor's pooled ln_post output), proj [D, E] (visual.proj), txt [C, E] text features that are ALREADY L2-normalised (they are
+ *      not normalised again), scale = exp(logit_scale):  u = feat . proj,  n = u / |u|,  logits [B, C] = scale * n . txt^T.  Saves u [B, E] and
+ *      inv_norm [B] = 1 / |u| for the backward.  As in the reference NO eps guards the norm: a row with u = 0 gives inf / NaN and is the caller's problem.
+ * bwd: dlogits [B, C] -> dfeat [B, D] = proj . ((g - n (n . g)) / |u|),  g = scale * dlogits . txt.  proj and txt take no gradient here (the text tower
+ *      and visual.proj are frozen on this path).
+ * All outputs are WRITTEN.  B, D, E, C >= 1, D + E <= 4096 and E + C <= 4096 (one row of each in LDS).  CE and predictions stay on clhip_ce_slice /
+ * the argmax of the head (ties to the lower index). */
+int clhip_clip_logits_fwd(const float* feat, const float* proj, const float* txt, float scale, float* logits, float* u, float* inv_norm, int B, int D, int E,
+                          int C, void* stream);
+int clhip_clip_logits_bwd(const float* dlogits, const float* proj, const float* txt, float scale, const float* u, const float* inv_norm, float* dfeat, int B,
+                          int D, int E, int C, void* stream);
 /* debug/test: copy one saved tensor of layer l of the last forward to fp32: 0 x_in [M, D] (layer == depth: the last block's output), 1 qkv [M, 3D],
  * 2 attn out, 3 x_mid, 4 GELU derivative of the mlp [M, mlp], 5 h1 = the LN1 output [M, D], 6 lse [B, H, N], 7 the LN1 statistics [2, M] (mean row, rstd
  * row), 8 the LN2 statistics likewise, 9 the adapter's dropped hidden rows [M, R].  0..4 and 6..9 need a forward that saved for the backward; 5 needs h1 to

@@ -238,6 +238,9 @@ _PROTOS = {
     "clhip_vit_sdlora_refresh": (_i, [_p, C.POINTER(VitParams), _p, _p]),
     "clhip_vit_lora_refresh_ab": (_i, [_p, C.POINTER(VitParams), _p, _p]),
     "clhip_vit_set_prefix": (_i, [_p, _p, _p, _p]),
+    "clhip_vit_set_clip": (_i, [_p, _p, _p, _f, _i]),
+    "clhip_clip_logits_fwd": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "clhip_clip_logits_bwd": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_project": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_rp_gram_accum": (_i, [_p, _p, _i, _i, _p]),
     "clhip_rp_label_sum": (_i, [_p, _p, _p, _i, _i, _i, _p]),

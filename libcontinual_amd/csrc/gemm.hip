@@ -20,7 +20,9 @@
 
 namespace {
 
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4 };
+enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4, EPI_BIAS_QGELU = 6 };      // 5 stays an unknown epilogue (the argument tests pin its refusal)
+constexpr bool epi_has_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_RES || e == EPI_BIAS_GELU || e == EPI_BIAS_QGELU; }
+constexpr bool epi_is_act(int e) { return e == EPI_BIAS_GELU || e == EPI_BIAS_QGELU; }
 
 struct GemmParams {
     const void* A; const void* B; void* C;
@@ -133,11 +135,29 @@ __device__ __forceinline__ void gelu_both2(f2 x, f2& y, f2& dy) {
     dy = x * 0.3989422804014327f * e + phi;
 }
 
+// QuickGELU of CLIP (transformer.py:137-139): y = x s, y' = s (1 + 1.702 x (1 - s)), s = sigmoid(1.702 x).  With t = 1.702 x and e = exp(-|t|) <= 1,
+// r = 1 / (1 + e): sigmoid(|t|) = r and sigmoid(-|t|) = e r = 1 - sigmoid(|t|), so ONE exp gives s AND 1 - s without cancellation, nothing overflows
+// (e underflows to 0 for |t| > ~103: s = 1 or 0, y' = 1 or 0) and no 0 * inf can form.
+__device__ __forceinline__ void qgelu_both2(f2 x, f2& y, f2& dy) {
+    const f2 t = x * 1.702f;
+    const f2 e = {__expf(-fabsf(t.x)), __expf(-fabsf(t.y))};
+    const f2 den = e + 1.0f;
+    const f2 r = {__frcp_rn(den.x), __frcp_rn(den.y)};
+    const f2 er = e * r;
+    const f2 s = {t.x >= 0.f ? r.x : er.x, t.y >= 0.f ? r.y : er.y};
+    const f2 c = {t.x >= 0.f ? er.x : r.x, t.y >= 0.f ? er.y : r.y};      // 1 - s
+    y = x * s;
+    dy = t * s * c + s;
+}
+template <int EPI> __device__ __forceinline__ void act_both2(f2 x, f2& y, f2& dy) {
+    if constexpr (EPI == EPI_BIAS_QGELU) qgelu_both2(x, y, dy); else gelu_both2(x, y, dy);
+}
+
 // epilogue of one accumulator: the lane holds C[m][n .. n+3]
 template <typename T, int EPI>
 __device__ __forceinline__ void epi_store(const GemmParams& p, const f32x4& a, int m, int n) {
     float v[4] = {a[0], a[1], a[2], a[3]};
-    if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RES || EPI == EPI_BIAS_GELU) {
+    if constexpr (epi_has_bias(EPI)) {
         const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
         v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
     }
@@ -147,11 +167,11 @@ __device__ __forceinline__ void epi_store(const GemmParams& p, const f32x4& a, i
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += r[e];
     }
-    if constexpr (EPI == EPI_BIAS_GELU) {
+    if constexpr (epi_is_act(EPI)) {
         float d[4];
         f2 y0, d0, y1, d1;
-        gelu_both2((f2){v[0], v[1]}, y0, d0);
-        gelu_both2((f2){v[2], v[3]}, y1, d1);
+        act_both2<EPI>((f2){v[0], v[1]}, y0, d0);
+        act_both2<EPI>((f2){v[2], v[3]}, y1, d1);
         v[0] = y0.x; v[1] = y0.y; v[2] = y1.x; v[3] = y1.y;
         d[0] = d0.x; d[1] = d0.y; d[2] = d1.x; d[3] = d1.y;
         if (p.H) store4<T>(static_cast<T*>(p.H) + (size_t)m * p.ldh + n, d);
@@ -331,7 +351,7 @@ __global__ __launch_bounds__(64 * WM * WN, (sizeof(T) == 2 && WM * WN == 4) ? 2 
             __syncthreads();
         }
         float4 bias4[NT];
-        if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES) {
+        if constexpr (epi_has_bias(EPI)) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int n = n0 + wn * 16 * NT + j * 16 + g * 4;
@@ -344,17 +364,17 @@ __global__ __launch_bounds__(64 * WM * WN, (sizeof(T) == 2 && WM * WN == 4) ? 2 
             for (int j = 0; j < NT; ++j) {
                 char* slot = smem + (wm * 16 * MT + i * 16 + l15) * CP + (wn * 16 * NT + j * 16 + g * 4) * 2;
                 float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES) { v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w; }
+                if constexpr (epi_has_bias(EPI)) { v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w; }
                 if constexpr (EPI == EPI_BIAS_RES) {
                     float r[4];
                     load4<T>(reinterpret_cast<const T*>(slot), r);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] += r[e];
                 }
-                if constexpr (EPI == EPI_BIAS_GELU) {
+                if constexpr (epi_is_act(EPI)) {
                     f2 y0, d0, y1, d1;
-                    gelu_both2((f2){v[0], v[1]}, y0, d0);
-                    gelu_both2((f2){v[2], v[3]}, y1, d1);
+                    act_both2<EPI>((f2){v[0], v[1]}, y0, d0);
+                    act_both2<EPI>((f2){v[2], v[3]}, y1, d1);
                     v[0] = y0.x; v[1] = y0.y; v[2] = y1.x; v[3] = y1.y;
                     // GELU' leaves directly (a second staged pass would have to keep or recompute it).  Round 5 measured the alternatives on fc1 of ViT-B/16 at
                     // M = 25216 (this form: 239 us, the plain product 155-158): both outputs through LDS in two half-tile passes with coalesced 16-byte stores,
@@ -613,6 +633,7 @@ template <typename T> int dispatch(int epi, const GemmParams& p, const Route& r,
         case EPI_BIAS_RES: return run_route<T, EPI_BIAS_RES>(p, r, s);
         case EPI_BIAS_GELU: return run_route<T, EPI_BIAS_GELU>(p, r, s);
         case EPI_MUL: return run_route<T, EPI_MUL>(p, r, s);
+        case EPI_BIAS_QGELU: return run_route<T, EPI_BIAS_QGELU>(p, r, s);
     }
     clhip_set_error("clhip_gemm_nt: unknown epilogue %d", epi);
     return CLHIP_EINVAL;
@@ -650,7 +671,7 @@ extern "C" int clhip_gemm_nt_route(int M, int N, int K, int lda, int ldb, int ld
 extern "C" int clhip_gemm_nt(const void* A, const void* B, void* C, const float* bias, const void* R, void* H, int M, int N, int K,
                              int lda, int ldb, int ldc, int ldr, int ldh, int epilogue, int dtype, void* stream) {
     CLHIP_CHECK_ARG(A && B && C);
-    if (epilogue == EPI_BIAS || epilogue == EPI_BIAS_RES || epilogue == EPI_BIAS_GELU) CLHIP_CHECK_ARG(bias != nullptr);
+    if (epi_has_bias(epilogue)) CLHIP_CHECK_ARG(bias != nullptr);
     if (epilogue == EPI_BIAS_RES) CLHIP_CHECK_ARG(R != nullptr);
     if (epilogue == EPI_MUL) CLHIP_CHECK_ARG(H != nullptr);
     if (int rc = check_shape(M, N, K, lda, ldb, ldc, ldr, ldh, dtype, R != nullptr, H != nullptr)) return rc;

@@ -40,7 +40,8 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) void lvoid_t;
 typedef __attribute__((ext_vector_type(2))) float f2;
 
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4 };
+enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4, EPI_BIAS_QGELU = 6 };      // 5 stays an unknown epilogue (the argument tests pin its refusal)
+constexpr bool epi_is_act(int e) { return e == EPI_BIAS_GELU || e == EPI_BIAS_QGELU; }
 
 struct Gemm8Params {
     const bf16_t* A; const bf16_t* B; bf16_t* C;
@@ -78,6 +79,19 @@ __device__ __forceinline__ void gelu_both8(f2 x, f2& y, f2& dy) {
     const f2 phi = se * 0.5f + 0.5f;
     y = x * phi;
     dy = x * 0.3989422804014327f * e + phi;
+}
+
+// QuickGELU and its derivative from one exp of -|1.702 x| (the derivation is at qgelu_both2 in gemm.hip; the two are the same arithmetic)
+__device__ __forceinline__ void qgelu_both8(f2 x, f2& y, f2& dy) {
+    const f2 t = x * 1.702f;
+    const f2 e = {__expf(-fabsf(t.x)), __expf(-fabsf(t.y))};
+    const f2 den = e + 1.0f;
+    const f2 r = {__frcp_rn(den.x), __frcp_rn(den.y)};
+    const f2 er = e * r;
+    const f2 s = {t.x >= 0.f ? r.x : er.x, t.y >= 0.f ? r.y : er.y};
+    const f2 c = {t.x >= 0.f ? er.x : r.x, t.y >= 0.f ? er.y : r.y};      // 1 - s
+    y = x * s;
+    dy = t * s * c + s;
 }
 
 __device__ __forceinline__ void unpack4_8(uint2 v, float (&f)[4]) {
@@ -225,7 +239,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const Gemm8Params p) {
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int n = nb + 8 * g4 + 4 * kh;
                 float v[4] = {a[4 * g4], a[4 * g4 + 1], a[4 * g4 + 2], a[4 * g4 + 3]};
-                if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RES || EPI == EPI_BIAS_GELU) {
+                if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RES || epi_is_act(EPI)) {
                     const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
                     v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
                 }
@@ -239,11 +253,11 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const Gemm8Params p) {
             }
         }
         float dv[16];
-        if constexpr (EPI == EPI_BIAS_GELU) {
+        if constexpr (epi_is_act(EPI)) {
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 f2 y, d;
-                gelu_both8((f2){a[r], a[r + 1]}, y, d);
+                if constexpr (EPI == EPI_BIAS_QGELU) qgelu_both8((f2){a[r], a[r + 1]}, y, d); else gelu_both8((f2){a[r], a[r + 1]}, y, d);
                 a[r] = y.x; a[r + 1] = y.y; dv[r] = d.x; dv[r + 1] = d.y;
             }
         }
@@ -258,7 +272,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const Gemm8Params p) {
                 auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
                 if (mv) *reinterpret_cast<u32x4*>(crow + pr * 16 + kh * 8) = u32x4{rx[0], ry[0], rx[1], ry[1]};
             }
-            if constexpr (EPI == EPI_BIAS_GELU) {
+            if constexpr (epi_is_act(EPI)) {
                 unsigned ax = pack_bf16x2(dv[8 * pr + 0], dv[8 * pr + 1]), ay = pack_bf16x2(dv[8 * pr + 2], dv[8 * pr + 3]);
                 unsigned bx = pack_bf16x2(dv[8 * pr + 4], dv[8 * pr + 5]), by = pack_bf16x2(dv[8 * pr + 6], dv[8 * pr + 7]);
                 auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
@@ -454,6 +468,7 @@ int clhip_gemm8_launch(const void* A, const void* B, void* C, const float* bias,
         case EPI_BIAS_RES: return launch8<EPI_BIAS_RES>(p, st);
         case EPI_BIAS_GELU: return launch8<EPI_BIAS_GELU>(p, st);
         case EPI_MUL: return launch8<EPI_MUL>(p, st);
+        case EPI_BIAS_QGELU: return launch8<EPI_BIAS_QGELU>(p, st);
     }
     clhip_set_error("gemm8: unknown epilogue %d", epilogue);
     return CLHIP_EINVAL;

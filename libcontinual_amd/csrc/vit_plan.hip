@@ -1,6 +1,6 @@
 // vit_plan.hip -- whole-backbone executor for the ViT path: one C call runs the complete forward (patch embedding,
 // token assembly with optional L2P prompt tokens, depth x [LN -> qkv -> attention -> proj(+res) -> LN -> fc1(GELU)
-// -> fc2(+res)], final LN + pooling) or the complete activation-gradient backward (every weight of the backbone is
+// -> fc2(+res)], final LN + pooling; CLIP's visual tower through clhip_vit_set_clip: ln_pre, QuickGELU, its own final eps) or the complete activation-gradient backward (every weight of the backbone is
 // frozen in L2P and InfLoRA_OPT; the only parameter gradients are the prompt tokens, the LoRA B matrices and, with adapter_dim > 0, the
 // AdaptFormer adapters of csrc/adapter.hip -- RanPAC's first session).
 // Replaces VisionTransformer.forward / Transformer.forward / ResidualAttentionBlock.forward
@@ -14,7 +14,7 @@
 namespace {
 size_t al(size_t v) { return (v + 255) / 256 * 256; }
 
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4 };
+enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_RES = 2, EPI_BIAS_GELU = 3, EPI_MUL = 4, EPI_BIAS_QGELU = 6 };
 
 struct LayerShadow { size_t qkv_f, qkv_b, proj_f, proj_b, fc1_f, fc1_b, fc2_f, fc2_b, acat; };
 
@@ -25,6 +25,7 @@ struct Layout {          // byte offsets into the workspace for one (B, n_prompt
     std::vector<size_t> x_in, x_mid, qkv, attn_o, hpre, h1, st1, st2, lse, ad_hd;   // per layer (x_in has depth+1 entries)
     std::vector<int> pf_lp;                  // prefix mode of the forward that filled this layout (empty = off): per layer the prefix length ...
     std::vector<const void*> pf_pk, pf_pv;   // ... and the caller's key / value rows, which the backward reads again
+    float final_eps;                         // eps of the pooled final LN of that forward (1e-6, or clhip_vit_set_clip's)
 };
 
 template <typename T>
@@ -54,6 +55,10 @@ struct clhip_vit {
     float* tap;                            // gradient tap (clhip_vit_set_tap; nullptr = off): host bookkeeping and copies only
     size_t tap_cap;
     int info_side, info_lowest;            // what the last backward did (clhip_vit_last_backward_info; -1 = none yet)
+    bool clip_on;                          // CLIP mode (clhip_vit_set_clip): ln_pre on the assembled tokens (NULL = none), QuickGELU in the MLP, ...
+    const float *clip_ln_w, *clip_ln_b;
+    float clip_final_eps;                  // ... and the eps of the pooled final LN
+    int clip_qgelu;
 };
 
 // The tap's slot map for the layout of the last saved forward, in floats.  Slot 0 holds g after ln_pool_bwd [M, D]; layer l's slots follow at
@@ -176,6 +181,7 @@ extern "C" clhip_vit* clhip_vit_create(const clhip_vit_desc* desc, int dtype) {
     v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = 0.f;
     v->sd_terms = v->sd_sum = 0; v->sd_factors = nullptr; v->sd_mag = v->sd_inv = nullptr;
     v->tap = nullptr; v->tap_cap = 0; v->info_side = v->info_lowest = -1;
+    v->clip_on = false; v->clip_ln_w = v->clip_ln_b = nullptr; v->clip_final_eps = 1e-6f; v->clip_qgelu = 0;
     return v;
 }
 
@@ -241,6 +247,18 @@ extern "C" int clhip_vit_set_prefix(clhip_vit* v, const int* Lp, const void* con
     return CLHIP_OK;
 }
 
+extern "C" int clhip_vit_set_clip(clhip_vit* v, const float* ln_pre_w, const float* ln_pre_b, float final_eps, int quick_gelu) {
+    CLHIP_CHECK_ARG(v != nullptr && (ln_pre_w != nullptr) == (ln_pre_b != nullptr) && (quick_gelu == 0 || quick_gelu == 1));
+    if (ln_pre_w == nullptr && quick_gelu == 0) {             // off: the executor is what it was
+        v->clip_on = false; v->clip_ln_w = v->clip_ln_b = nullptr; v->clip_final_eps = 1e-6f; v->clip_qgelu = 0;
+        return CLHIP_OK;
+    }
+    CLHIP_CHECK_ARG(final_eps > 0.f);
+    CLHIP_CHECK_ARG(v->d.adapter_dim == 0 && v->sd_terms == 0 && v->pf_lp.empty());      // (a forward checks again: those modes may be set afterwards)
+    v->clip_on = true; v->clip_ln_w = ln_pre_w; v->clip_ln_b = ln_pre_b; v->clip_final_eps = final_eps; v->clip_qgelu = quick_gelu;
+    return CLHIP_OK;
+}
+
 extern "C" int clhip_vit_sdlora_refresh(clhip_vit* v, const clhip_vit_params* P, void* shadow, void* stream) {
     CLHIP_CHECK_ARG(v && P && P->layers && shadow && v->sd_terms > 0);
     char* sh = static_cast<char*>(shadow);
@@ -300,8 +318,13 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
     CLHIP_CHECK_ARG(n_prompt == 0 || prompt_tokens != nullptr);
     CLHIP_CHECK_ARG(n_prompt + 1 + v->np <= 256);
     const clhip_vit_desc& d = v->d;
+    const bool clip = v->clip_on;
+    // CLIP mode: no prompt tokens, prefixes, adapters or SD-LoRA (none of the reference's CLIP methods combines them); refused before any launch
+    if (clip) CLHIP_CHECK_ARG(n_prompt == 0 && v->pf_lp.empty() && d.adapter_dim == 0 && v->sd_terms == 0);
+    CLHIP_CHECK_ARG(clip || P->pe_b != nullptr);
     Layout& L = v->last;
     make_layout(v, B, n_prompt, (save ? 1 : 0) | (gram ? 2 : 0), L);
+    L.final_eps = clip ? v->clip_final_eps : 1e-6f;
     L.pf_lp = v->pf_lp; L.pf_pk = v->pf_pk; L.pf_pv = v->pf_pv;                  // (make_layout leaves them alone: the mode of THIS forward)
     v->have_last = true;
     char* ws = static_cast<char*>(workspace);
@@ -314,8 +337,17 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
     v->drop_seed = nullptr; v->drop_p = 0.f; v->last_p = drop_p;             // the dropout state is consumed by this forward
     // patch embedding (timm PatchEmbed = Conv2d(3, D, p, stride p)) as patchify + GEMM, then token assembly
     TRY(clhip_patchify(images, ws + L.patches, B, d.img, d.patch, dt, stream));
-    TRY(clhip_gemm_nt(ws + L.patches, sh + v->pe_f, ws + L.pe_out, P->pe_b, nullptr, nullptr, B * v->np, D, v->Kp, v->Kp, v->Kp, D, 0, 0, EPI_BIAS, dt, stream));
-    TRY(clhip_vit_assemble(ws + L.pe_out, P->cls_token, P->pos_embed, prompt_tokens, ws + L.x_in[0], B, v->np, n_prompt, D, dt, stream));
+    // (CLIP's conv1 has no bias, transformer.py:2107: pe_b == NULL there)
+    TRY(clhip_gemm_nt(ws + L.patches, sh + v->pe_f, ws + L.pe_out, P->pe_b, nullptr, nullptr, B * v->np, D, v->Kp, v->Kp, v->Kp, D, 0, 0,
+                      P->pe_b ? EPI_BIAS : EPI_NONE, dt, stream));
+    if (clip && v->clip_ln_w) {
+        // ln_pre (transformer.py:2127, eps 1e-5): the assembled rows land in the LN scratch, which nothing owns before layer 0, and x_in[0] is their
+        // normalised form.  Nothing below it takes a gradient (no prompt tokens in this mode), so no statistics are kept and there is no backward.
+        TRY(clhip_vit_assemble(ws + L.pe_out, P->cls_token, P->pos_embed, nullptr, ws + L.ln_out, B, v->np, 0, D, dt, stream));
+        TRY(clhip_ln_fwd(ws + L.ln_out, v->clip_ln_w, v->clip_ln_b, ws + L.x_in[0], nullptr, nullptr, M, D, 1e-5f, dt, stream));
+    } else
+        TRY(clhip_vit_assemble(ws + L.pe_out, P->cls_token, P->pos_embed, prompt_tokens, ws + L.x_in[0], B, v->np, n_prompt, D, dt, stream));
+    const int epi_act = clip && v->clip_qgelu ? EPI_BIAS_QGELU : EPI_BIAS_GELU;
     for (int l = 0; l < d.depth; ++l) {
         const clhip_vit_layer_params& p = P->layers[l];
         const LayerShadow& s = v->sh[l];
@@ -331,7 +363,7 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
             TRY(clhip_attn_fwd(ws + L.qkv[l], ws + L.attn_o[l], reinterpret_cast<float*>(ws + L.lse[l]), B, N, d.heads, D, dt, stream));
         TRY(clhip_gemm_nt(ws + L.attn_o[l], sh + s.proj_f, ws + L.x_mid[l], p.proj_b, ws + L.x_in[l], nullptr, M, D, D, D, D, D, D, 0, EPI_BIAS_RES, dt, stream));
         TRY(clhip_ln_fwd(ws + L.x_mid[l], p.ln2_w, p.ln2_b, ws + L.ln_out, st2, st2 + M, M, D, beps, dt, stream));
-        TRY(clhip_gemm_nt(ws + L.ln_out, sh + s.fc1_f, ws + L.act, p.fc1_b, nullptr, save ? ws + L.hpre[l] : nullptr, M, Hm, D, D, D, Hm, 0, Hm, EPI_BIAS_GELU, dt,
+        TRY(clhip_gemm_nt(ws + L.ln_out, sh + s.fc1_f, ws + L.act, p.fc1_b, nullptr, save ? ws + L.hpre[l] : nullptr, M, Hm, D, D, D, Hm, 0, Hm, epi_act, dt,
                           stream));
         TRY(clhip_gemm_nt(ws + L.act, sh + s.fc2_f, ws + L.x_in[l + 1], p.fc2_b, ws + L.x_mid[l], nullptr, M, D, Hm, Hm, Hm, D, D, 0, EPI_BIAS_RES, dt, stream));
         if (R > 0) {                                         // x_out += s * adapter(x_mid), parallel to the MLP (vision_transformer_adapter.py:165-183)
@@ -347,7 +379,7 @@ extern "C" int clhip_vit_forward(clhip_vit* v, const clhip_vit_params* P, const 
         if (strided && d.depth > 1) TRY(clhip_gram_accum_batched(ws + L.h1[0], (L.h1[1] - L.h1[0]) / v->esize, d.depth, gram, M, D, dt, stream));
         else for (int l = 0; l < d.depth; ++l) TRY(clhip_gram_accum(ws + L.h1[l], gram + (size_t)l * D * D, M, D, dt, stream));
     }
-    return clhip_ln_pool_fwd(ws + L.x_in[d.depth], P->norm_w, P->norm_b, feat, B, N, D, n_prompt > 0 ? n_prompt : 1, 1e-6f, dt, stream);
+    return clhip_ln_pool_fwd(ws + L.x_in[d.depth], P->norm_w, P->norm_b, feat, B, N, D, n_prompt > 0 ? n_prompt : 1, L.final_eps, dt, stream);
 }
 
 // the leaves (d_lora_b, d_sd, d_ab) exclude one another; dpk / dpv are required exactly when the saved forward ran in prefix mode
@@ -409,7 +441,7 @@ extern "C" int clhip_vit_backward(clhip_vit* v, const clhip_vit_params* P, const
         return n ? vit_to_f32(src, v->tap + tap_slot_off(v, L, layer, slot), n, dt, main_s) : CLHIP_OK;
     };
     v->info_side = side_on ? 1 : 0; v->info_lowest = -1;
-    TRY(clhip_ln_pool_bwd(dfeat, ws + L.x_in[d.depth], P->norm_w, g, B, N, D, L.P > 0 ? L.P : 1, 1e-6f, dt, stream));
+    TRY(clhip_ln_pool_bwd(dfeat, ws + L.x_in[d.depth], P->norm_w, g, B, N, D, L.P > 0 ? L.P : 1, L.final_eps, dt, stream));
     TRY(tap(g, -1, 0));
     for (int l = d.depth - 1; l >= 0; --l) {
         const clhip_vit_layer_params& p = P->layers[l];

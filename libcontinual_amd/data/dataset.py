@@ -28,6 +28,10 @@ class SingleDataset(Dataset):
                     self.images.append(os.path.join(name, f))
                     self.labels.append(label)
 
+    def get_class_names(self):
+        """the task's class names in label order (dataset.py:303-304)"""
+        return list(self.labels_name)
+
     def __len__(self):
         return len(self.labels)
 
@@ -75,15 +79,22 @@ class ArrayDataset(Dataset):
     every per-task view (and by copies of a view); `device_store()` uploads it once and keeps it resident for the GPU input
     pipeline."""
 
-    def __init__(self, store, images, labels, trfms, mode="train", resident=None):
+    def __init__(self, store, images, labels, trfms, mode="train", resident=None, labels_name=None):
         self.store, self.trfms, self.mode, self.data_root = store, trfms, mode, None
         self.images, self.labels = list(images), list(labels)
+        self.labels_name = None if labels_name is None else list(labels_name)      # the view's class names in label order (None: the data has none)
         self._resident = resident if resident is not None else {}       # device -> uint8 tensor, shared between views
 
     def __deepcopy__(self, memo):
         """views are copied (the trainer and the plugins edit `images` / `labels` of copies), the image store and its device
         copy are shared"""
-        return ArrayDataset(self.store, list(self.images), list(self.labels), self.trfms, self.mode, self._resident)
+        return ArrayDataset(self.store, list(self.images), list(self.labels), self.trfms, self.mode, self._resident, self.labels_name)
+
+    def get_class_names(self):
+        """the task's class names in label order, as SingleDataset gives them"""
+        if self.labels_name is None:
+            raise ValueError("this dataset carries no class names")
+        return list(self.labels_name)
 
     def device_store(self, device):
         key = str(device)
@@ -180,7 +191,7 @@ def preloaded_datasets(config, mode, trfms, bs, cls_map, device):
 
     def mk(s, e):
         idx = np.flatnonzero((labels >= s) & (labels < e))
-        return ArrayDataset(store, idx.tolist(), labels[idx].tolist(), trfms, mode, shared)
+        return ArrayDataset(store, idx.tolist(), labels[idx].tolist(), trfms, mode, shared, [cls_map[l] for l in range(s, e)])
     return ContinualDatasets(mode, config["task_num"], config["init_cls_num"], config["inc_cls_num"], mk, bs, config["num_workers"], cls_map, device)
 
 
@@ -213,5 +224,5 @@ def synthetic_datasets(config, mode, trfms, bs, device=None):
 
     def mk(s, e):
         idx = [i for i in range(len(labels)) if s <= labels[i] < e]
-        return ArrayDataset(store, idx, [int(labels[i]) for i in idx], trfms, mode, shared)
+        return ArrayDataset(store, idx, [int(labels[i]) for i in idx], trfms, mode, shared, [f"class {l}" for l in range(s, e)])
     return ContinualDatasets(mode, config["task_num"], config["init_cls_num"], config["inc_cls_num"], mk, bs, 0, None, device)

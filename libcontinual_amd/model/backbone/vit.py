@@ -454,15 +454,14 @@ class VisionTransformer(nn.Module):
         self.lora_sub = attn_layer is MultiHeadAttention_LoRA_Sub
         self.lora_rank = lora_rank if attn_layer is MultiHeadAttention_LoRA or self.lora_sub else 0
         self.compute_dtype = dtype
-        self.patch_embed = _PatchEmbed(img_size, patch_size, in_chans, embed_dim)
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
-        self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + 1, embed_dim))
+        self.num_patches = (img_size // patch_size) ** 2
+        self._make_stem(img_size, patch_size, in_chans, embed_dim)
         self.sd_lora = attn_layer is MultiHeadAttention_SDLoRA
         kw = {"lora_rank": lora_rank} if self.lora_rank or self.sd_lora else {}
         if self.lora_sub:
             kw["lora_bias"] = kwargs.get("lora_bias", False)
         self.transformer = Transformer(embed_dim, depth, num_heads, mlp_ratio, attn_layer, **kw)
-        self.norm = _P((embed_dim,))
+        self._make_final_norm(embed_dim)
         self._s = _Scratch()
         self._fwd_token = 0
         self.reset_parameters()
@@ -483,14 +482,33 @@ class VisionTransformer(nn.Module):
             for blk in self.transformer.blocks:
                 blk.adaptmlp = Adapter(embed_dim, self.adapter_dim, self.adapter_scale, self.adapter_dropout)
 
-    # ------------------------------------------------------------------ init (transformer.py:2201-2213, timm PatchEmbed)
-    def reset_parameters(self):
+    # ------------------------------------------------------------------ the parts a sibling tower names differently (backbone/clip.py: VisualTransformer)
+    def _make_stem(self, img_size, patch_size, in_chans, embed_dim):
+        self.patch_embed = _PatchEmbed(img_size, patch_size, in_chans, embed_dim)
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + 1, embed_dim))
+
+    def _make_final_norm(self, embed_dim):
+        self.norm = _P((embed_dim,))
+
+    def _reset_stem(self):
         nn.init.trunc_normal_(self.pos_embed, std=.02)
         nn.init.trunc_normal_(self.cls_token, std=.02)
         w = self.patch_embed.proj.weight
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))
         bound = 1 / math.sqrt(w[0].numel())
         nn.init.uniform_(self.patch_embed.proj.bias, -bound, bound)
+
+    def _reset_final_norm(self):
+        nn.init.ones_(self.norm.weight); nn.init.zeros_(self.norm.bias)
+
+    def _stem_tensors(self):
+        """(cls token, positional embedding, patch weight, patch bias or None, final norm weight, final norm bias): the executor's clhip_vit_params"""
+        return self.cls_token, self.pos_embed, self.patch_embed.proj.weight, self.patch_embed.proj.bias, self.norm.weight, self.norm.bias
+
+    # ------------------------------------------------------------------ init (transformer.py:2201-2213, timm PatchEmbed)
+    def reset_parameters(self):
+        self._reset_stem()
         for blk in self.transformer.blocks:
             for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2):
                 nn.init.trunc_normal_(lin.weight, std=.02)
@@ -500,7 +518,7 @@ class VisionTransformer(nn.Module):
             if self.lora_rank:
                 for n in ("lora_A_k", "lora_B_k", "lora_A_v", "lora_B_v"):
                     nn.init.trunc_normal_(getattr(blk.attn, n).weight, std=.02)
-        nn.init.ones_(self.norm.weight); nn.init.zeros_(self.norm.bias)
+        self._reset_final_norm()
 
     # ------------------------------------------------------------------------------------ executor state
     def attention_modules(self):
@@ -515,7 +533,7 @@ class VisionTransformer(nn.Module):
         return b.attn.executor_weight() if self.lora_sub else b.attn.qkv.weight
 
     def _frozen_tensors(self):
-        out = [self.patch_embed.proj.weight]
+        out = [self._stem_tensors()[2]]
         for b in self.transformer.blocks:
             out += [self._qkv_master(b), b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight]
         return out
@@ -558,8 +576,7 @@ class VisionTransformer(nn.Module):
                     L.lora_a_v, L.lora_b_v = b.attn.lora_A_v.weight.data_ptr(), b.attn.lora_B_v.weight.data_ptr()
                 if self.adapter_dim:
                     L.ad_down_w, L.ad_down_b, L.ad_up_w, L.ad_up_b = [t.data_ptr() for t in b.adaptmlp.tensors()]
-            cp = _lib.VitParams(self.cls_token.data_ptr(), self.pos_embed.data_ptr(), self.patch_embed.proj.weight.data_ptr(),
-                                self.patch_embed.proj.bias.data_ptr(), self.norm.weight.data_ptr(), self.norm.bias.data_ptr(), layers)
+            cp = _lib.VitParams(*[None if t is None else t.data_ptr() for t in self._stem_tensors()], layers)
             s.cparams, s.keep, s.layers = cp, ptrs, layers
             s.sig = None
         lora_on = bool(self.lora_rank) and any(a.apply_lora for a in self.attention_modules())
@@ -725,7 +742,7 @@ class VisionTransformer(nn.Module):
             G.d_sd, G.d_mag_rows, G.d_mag = _ptrs(fac), rows.data_ptr(), dmag.data_ptr()
             out["sd"] = fac + [dmag[i:i + 1] for i in range(T1)]
         if "ab" in want:
-            r, need = self.lora_rank, _lib.lib().clhip_lora_grad_ab_ws_bytes(B * (n_prompt + 1 + self.patch_embed.num_patches), D)
+            r, need = self.lora_rank, _lib.lib().clhip_lora_grad_ab_ws_bytes(B * (n_prompt + 1 + self.num_patches), D)
             if s.ab_grads is None or s.ab_grads.device != dev:
                 s.ab_grads = torch.empty(depth, 4 * r * D, device=dev)
             if s.ab_ws is None or s.ab_ws.device != dev or s.ab_ws.numel() < need:
@@ -819,7 +836,7 @@ class VisionTransformer(nn.Module):
         feat = _VitFn.apply(self, images, prompt_tokens, gram, need, want, *lora_b, *adapters)
         if get_input_matrix and gram_out is None:
             # the running mean over tokens (transformer.py:241-244) is taken when `cur_matrix` is read; here only the token count moves
-            cnt = images.shape[0] * (self.patch_embed.num_patches + 1 + (0 if prompt_tokens is None else prompt_tokens.shape[0]))
+            cnt = images.shape[0] * (self.num_patches + 1 + (0 if prompt_tokens is None else prompt_tokens.shape[0]))
             for a in self.attention_modules():
                 g = a.__dict__.get("_gram")
                 if g is not None:
@@ -840,7 +857,7 @@ class VisionTransformer(nn.Module):
     def debug_read(self, layer, which):
         s = self._s
         B, n_prompt = self._last
-        N = n_prompt + 1 + self.patch_embed.num_patches
+        N = n_prompt + 1 + self.num_patches
         M = B * N
         D = self.embed_dim
         # include/clhip.h, clhip_vit_read_act: 5 the LN1 output, 6 lse [B, H, N], 7 / 8 the LN1 / LN2 statistics [2, M], 9 the adapter's hidden rows

@@ -1,4 +1,4 @@
-"""InfLoRA_OPT plugin (reference core/model/InfLoRA_opt.py:46-460, ViT branch) on the HIP ViT executor.
+"""InfLoRA_OPT plugin (reference core/model/InfLoRA_opt.py:46-460, ViT and CLIP branches) on the HIP ViT executor.
 
 Same constructor kwargs, hooks and quirks: every task re-zeroes all `lora_B`, fixes
 `lora_A` from the SVD of the (DualGPM-projected) input Gram, trains all `lora_B*` + the task's head
@@ -14,7 +14,12 @@ Classifier alignment (`use_ca: true`, InfLoRA_opt.py:285-288, :371-456): after e
 task 1 on all heads so far re-trained on draws from them -- class_align.ClassAligner on the kernels of csrc/ca.hip.  Two quirks of the reference
 are guards here: with any dataset but cifar100 its loss branch is an empty `pass` (:445-447) and the first step fails on an undefined `loss`; and
 both functions index classes as if init_cls_num == inc_cls_num (:377-381, :418-419).  The feature width is `embd_dim`, not the reference's literal 768.
-The CLIP branch is outside the hot-path scope.
+The CLIP branch (`backbone: clip`, `visual_only: true`; InfLoRA_opt.py:60-66, :74-85, :123-128, :137-138, :166-171, :229-235): LoRA on k and v of the visual
+tower only, a frozen text tower, CE on logit_scale * cos(image, text) against the text features of the running task's classes (training) or of all classes
+so far (inference).  There is no classifier_pool; the trainable parameters are the visual lora_B only.  The text tower is frozen, so `update_fc` computes
+the normalised text features of both class sets ONCE per task and keeps them (the reference recomputes identical values every step); a step is one executor
+forward in CLIP mode plus csrc/clip.hip.  Class names come from `train_loader.dataset.get_class_names()` through backbone/clip_tokenizer.py, or, without
+the merges file, from the kwarg `class_tokens` ([total classes, 77] int64 in label order).
 """
 import math
 import os
@@ -25,6 +30,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils import device_svd
+from .backbone.clip import CLIP
+from .backbone.clip_tokenizer import tokenize
 from .backbone.vit import MultiHeadAttention_LoRA, ViTZoo
 from .class_align import ClassAligner
 from .heads import HipLinear
@@ -36,29 +43,69 @@ class SiNet(nn.Module):
         self._cur_task_id = -1
         self.backbone = backbone
         self.device = device
+        self.is_clip = isinstance(backbone, CLIP)
+        if self.is_clip:
+            self.prompt_template = kwargs["prompt_template"]
+            self.accm_class_names, self.curr_class_names = [], []
+            self.accm_text_tokens = self.curr_text_tokens = None
+            self.accm_text_features = self.curr_text_features = None      # normalised, fp32, on the device: fixed for the task (frozen text tower)
+            self._class_tokens, self._bpe_path = kwargs.get("class_tokens"), kwargs.get("bpe_path")
+            self._task_sizes = [kwargs["init_cls_num"]] + [kwargs["inc_cls_num"]] * (kwargs["task_num"] - 1)
+            self._scale = None
+            if self._class_tokens is not None:
+                self._class_tokens = torch.as_tensor(self._class_tokens, dtype=torch.int64)
+                if self._class_tokens.dim() != 2 or self._class_tokens.shape[0] < sum(self._task_sizes):
+                    raise ValueError(f"class_tokens must be [>= {sum(self._task_sizes)} classes, context length] in label order, got {tuple(self._class_tokens.shape)}")
+            return
         if not isinstance(backbone, ViTZoo):
-            raise NotImplementedError("only the ViT backbone is on the hot path (SURVEY.md section 8)")
+            raise NotImplementedError("only the ViT and CLIP backbones are on the hot path (SURVEY.md section 8)")
         self.classifier_pool = nn.ModuleList(
             [HipLinear(kwargs["embd_dim"], kwargs["init_cls_num"], bias=True)] +
             [HipLinear(kwargs["embd_dim"], kwargs["inc_cls_num"], bias=True) for _ in range(kwargs["task_num"] - 1)])
 
+    @torch.no_grad()
     def update_fc(self, train_loader):
         self._cur_task_id += 1
+        if not self.is_clip:
+            return
+        t = self._cur_task_id
+        if self._class_tokens is not None:
+            known = sum(self._task_sizes[:t])
+            curr, accm = self._class_tokens[known:known + self._task_sizes[t]], self._class_tokens[:known + self._task_sizes[t]]
+        else:                                                            # InfLoRA_opt.py:76-85
+            self.curr_class_names = list(train_loader.dataset.get_class_names())
+            self.accm_class_names += self.curr_class_names
+            curr = tokenize([self.prompt_template.format(c) for c in self.curr_class_names], self.backbone.context_length, self._bpe_path)
+            accm = tokenize([self.prompt_template.format(c) for c in self.accm_class_names], self.backbone.context_length, self._bpe_path)
+        self.curr_text_tokens, self.accm_text_tokens = curr.to(self.device), accm.to(self.device)
+        self.curr_text_features = self.backbone.text_features(self.curr_text_tokens)
+        self.accm_text_features = self.backbone.text_features(self.accm_text_tokens)
+        self._scale = float(self.backbone.logit_scale.exp())             # frozen: read once per task, not once per step
 
     def get_feature(self, x):
+        if self.is_clip:
+            raise NotImplementedError("get_feature on the CLIP backbone is `assert 0` in the reference (InfLoRA_opt.py:88-94)")
         return self.backbone(x)
 
     def fc_only(self, x):
+        if self.is_clip:
+            raise NotImplementedError("fc_only on the CLIP backbone is `assert 0` in the reference (InfLoRA_opt.py:96-105)")
         return torch.cat([fc(x) for fc in self.classifier_pool[: self._cur_task_id + 1]], dim=1)
 
     def forward(self, x, inference=False):
+        if self.is_clip:                                                 # InfLoRA_opt.py:123-128
+            txt = self.accm_text_features if inference else self.curr_text_features
+            return self.backbone.image_logits(x, txt, self._scale)[0]
         features = self.backbone(x)
         heads = self.classifier_pool[: self._cur_task_id + 1] if inference else [self.classifier_pool[self._cur_task_id]]
         return torch.cat([fc(features) for fc in heads], dim=1)
 
     def update_input_matrix(self, x):
         with torch.no_grad():
-            self.backbone(x, get_input_matrix=True)
+            if self.is_clip:                                             # (InfLoRA_opt.py:137-138 also runs the text tower, whose Grams nobody reads)
+                self.backbone.visual.features(x, None, True)
+            else:
+                self.backbone(x, get_input_matrix=True)
 
 
 class InfLoRA_OPT(nn.Module):
@@ -85,8 +132,24 @@ class InfLoRA_OPT(nn.Module):
                 raise NotImplementedError(f"use_ca with init_cls_num {self.init_cls_num} != inc_cls_num {self.inc_cls_num}: _create_distribution and "
                                           "_compact_classifier index classes as if the two were equal (InfLoRA_opt.py:377-381, :418-419)")
             self._aligner = ClassAligner(kwargs["embd_dim"], device)
+        self._is_clip = isinstance(backbone, CLIP)
+        if self._is_clip:
+            if not kwargs.get("visual_only", False):
+                raise NotImplementedError("visual_only: false trains LoRA on the text tower too (InfLoRA_opt.py:170-171, :236-241): that needs a causal attention "
+                                          "forward / backward in the executor, which is not built")
+            if self._use_class_alignment:
+                raise NotImplementedError("use_ca with the CLIP backbone: the reference's get_feature / fc_only are `assert 0` there (InfLoRA_opt.py:88-105)")
+            if getattr(backbone, "lora_rank", 0) <= 0:
+                raise NotImplementedError("the CLIP backbone was built without lora_rank (or with 0): the reference's block default (transformer.py:1293) gives a "
+                                          "rank-0 LoRA, and InfLoRA_opt.py:256-257 has no row of lora_A to fill; set backbone.kwargs.lora_rank")
+            if int(kwargs.get("n_gpu", 1) or 1) > 1:
+                raise NotImplementedError("n_gpu > 1 with the CLIP backbone: data parallelism is not built on this backbone")
         self._network = SiNet(backbone, device, **kwargs).to(self.device)
-        self.attention_modules = [m for m in self._network.modules() if isinstance(m, MultiHeadAttention_LoRA)]
+        if self._is_clip:                                                # InfLoRA_opt.py:167-169: the visual tower's modules only
+            self.visual_only = True
+            self.attention_modules = [m for n, m in self._network.named_modules() if isinstance(m, MultiHeadAttention_LoRA) and "visual" in n]
+        else:
+            self.attention_modules = [m for m in self._network.modules() if isinstance(m, MultiHeadAttention_LoRA)]
 
     def observe(self, data):
         x, y = data["image"].to(self.device), data["label"].to(self.device) - self._known_classes
@@ -105,6 +168,8 @@ class InfLoRA_OPT(nn.Module):
 
     @torch.no_grad()
     def before_task(self, task_idx, buffer, train_loader, test_loaders):
+        if self._is_clip and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("n_gpu > 1 with the CLIP backbone: data parallelism is not built on this backbone")
         if task_idx == 1:
             self._known_classes = self.init_cls_num
         elif task_idx > 1:
@@ -114,7 +179,9 @@ class InfLoRA_OPT(nn.Module):
             module.init_param()
         for name, param in self._network.named_parameters():
             param.requires_grad_(False)
-            if f"classifier_pool.{task_idx}." in name or "lora_B" in name:
+            if self._is_clip:                                            # InfLoRA_opt.py:229-235
+                param.requires_grad_("visual" in name and "lora_B" in name)
+            elif f"classifier_pool.{task_idx}." in name or "lora_B" in name:
                 param.requires_grad_(True)
         for batch in train_loader:
             self._network.update_input_matrix(x=batch["image"].to(self.device))

@@ -104,6 +104,42 @@ def cosine_linear(x, w):
     return _CosineLinearFn.apply(x, w)
 
 
+class _ClipLogitsFn(torch.autograd.Function):
+    """logits = scale * normalize(feat @ proj) @ txt^T with txt already normalised (CLIP.forward, backbone/clip.py:405-412) via clhip_clip_logits_fwd / _bwd.
+    Differentiable w.r.t. feat only: visual.proj, the text features and logit_scale are frozen on this path."""
+
+    @staticmethod
+    def forward(ctx, feat, proj, txt, scale):
+        feat, proj, txt = _f32c(feat), _f32c(proj), _f32c(txt)
+        _dev(feat, proj, txt)
+        (B, D), E, Cn = feat.shape, proj.shape[1], txt.shape[0]
+        if proj.shape[0] != D or txt.shape[1] != E:
+            raise _lib.ClhipError(f"clip_logits: feat {tuple(feat.shape)}, proj {tuple(proj.shape)}, txt {tuple(txt.shape)} do not chain")
+        out = torch.empty(B, Cn, device=feat.device, dtype=torch.float32)
+        u = torch.empty(B, E, device=feat.device, dtype=torch.float32)
+        inv = torch.empty(B, device=feat.device, dtype=torch.float32)
+        call("clhip_clip_logits_fwd", _ptr(feat), _ptr(proj), _ptr(txt), float(scale), _ptr(out), _ptr(u), _ptr(inv), B, D, E, Cn, _st())
+        ctx.save_for_backward(proj, txt, u, inv)
+        ctx.scale = float(scale)
+        ctx.mark_non_differentiable(u, inv)
+        return out, u, inv
+
+    @staticmethod
+    def backward(ctx, dout, _du, _dinv):
+        proj, txt, u, inv = ctx.saved_tensors
+        dout = _f32c(dout)
+        (D, E), (B, Cn) = proj.shape, dout.shape
+        dfeat = torch.empty(B, D, device=dout.device, dtype=torch.float32)
+        call("clhip_clip_logits_bwd", _ptr(dout), _ptr(proj), _ptr(txt), ctx.scale, _ptr(u), _ptr(inv), _ptr(dfeat), B, D, E, Cn, _st())
+        return dfeat, None, None, None
+
+
+def clip_logits(feat, proj, txt, scale, with_saved=False):
+    """logits [B, C]; with_saved: also u = feat @ proj [B, E] and 1 / |u| [B] as the kernel saved them (no gradient flows through those two)"""
+    out, u, inv = _ClipLogitsFn.apply(feat, proj, txt, scale)
+    return (out, u, inv) if with_saved else out
+
+
 class _SigmaScaleFn(torch.autograd.Function):
     """logits = sigma * scores with sigma a 1-element parameter (backbone/resnet.py:439-441)."""
 
