@@ -319,6 +319,45 @@ int clhip_stage_eval_supported(int H, int W, int C, int nconv, int dtype);
 int clhip_stage_eval(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
                      const float* const* mean, const float* const* var, float eps, int dtype, void* stream);
 
+/* The same run in TRAINING mode as ONE launch per direction (csrc/stage_train.hip, csrc/xch.h): one workgroup per image, all of them resident at once, the batch
+ * statistics of every BatchNorm through an in-launch all-reduce.  These are the launches a bf16 plan makes of such a run (see clhip_plan_stage_status above for the
+ * rules a process must keep); the direct entries read no switch except STAGE_XCH3.  One entry per convolution in every table (host arrays of device pointers).
+ *   forward   x [N][H][W][C] bf16; w[i] the [C][9][C] forward copy of clhip_conv_weight_prep; gamma / beta[i] fp32 [C]; rm / rv[i] the running statistics, updated
+ *             in place (momentum, unbiased variance; factor 1 at N H W = 1); mean / invstd[i] [C] and coef[i] [2][C] (scale, shift) are written; z[i] [N][H][W][C]
+ *             bf16 the pre-BatchNorm output (entry NULL: not stored -- a forward no backward follows); y[i] the activation behind convolution i (NULL: not stored;
+ *             the launch itself needs none of them); mask[i] is accepted for the plan's sake and never written: the backward takes the ReLU mask of a block
+ *             output from y > 0.  feat (nullable) [N][C] fp32: the global average of the run's output.
+ *   backward  x as above, dy [N][H][W][C] bf16 the gradient of the run's output (not read when dfeat [N][C] is given: the gradient is then dfeat / (H W) at every
+ *             pixel), dx the gradient of x (dx_accumulate: added to what dx holds); wd[i] the [C][9][C] dgrad copy (w_dg of clhip_conv_weight_prep); mean / invstd /
+ *             z[i] as the forward left them, y[i] at the second convolution of every block (odd i), NULL elsewhere; dgamma / dbeta[i] are accumulated into;
+ *             slab[i]: clhip_stage_train_query(SLAB_BLOCKS) blocks of C * 9 * C floats, one per image or per group of 16 images, which the caller sums in block
+ *             order; dzg[i] [C / 16][N][H][W][16] bf16 scratch where the query reports the group form, NULL otherwise.
+ *   entry != 0: the launch starts with the stage's down-sampling block: nconv odd, C >= 32, the tables hold nconv + 2 entries -- [0] its 3x3 / stride-2 convolution
+ *             (w [C][9][C / 2], wd [C / 2][9][C], slab N blocks of C * 9 * C / 2), [1] its 1x1 / stride-2 shortcut (w [C][1][C / 2], wd [C / 2][1][C], slab N blocks of
+ *             C * C / 2; y[1] may receive the shortcut's BatchNorm output), [2] its second convolution, [3 ...] the blocks behind it; x / dx are [N][2 H][2 W][C / 2].
+ *   xch       clhip_stage_train_query(XCH_BYTES, N) bytes, zeroed ONCE by the caller and then reused by every launch at that N, whatever its direction or geometry.
+ *             clhip_stage_train_status returns its sticky error word (0 = clean; synchronises the device).
+ * Supported: bf16, (C, H = W) = (16, 32), (32, 16) or (64, 8), 1 <= N <= query(MAX_BATCH), nconv even in 2 .. 16 (entry: odd in 1 .. 15).  Anything else, or a NULL
+ * xch, is CLHIP_EINVAL before a launch. */
+#define CLHIP_STAGE_TRAIN_Q_MAX_BATCH 0   /* the largest N */
+#define CLHIP_STAGE_TRAIN_Q_XCH_BYTES 1   /* bytes of the exchange buffer for N */
+#define CLHIP_STAGE_TRAIN_Q_SLAB_BLOCKS 2 /* weight-gradient blocks per convolution that a backward of N images at C channels leaves */
+#define CLHIP_STAGE_TRAIN_Q_GROUP 3       /* 1: that backward takes the group weight gradient (and needs dzg) */
+#define CLHIP_STAGE_TRAIN_Q_FORM 4        /* the exchange of N workgroups at C channels under the current switches: 1 one hop, 2 two hops, 3 three levels (XCD-first) */
+/* -1: unknown `what`, N < 1, or (SLAB_BLOCKS, GROUP, FORM) a C other than 16 / 32 / 64; XCH_BYTES answers for any N >= 1, also beyond MAX_BATCH.
+ * The three-level form is taken only on a device whose XCD probe has RUN and found the rule to hold: clhip_plan_create runs it, and so does query(FORM) -- which
+ * is why FORM must not be asked inside a stream capture.  The launches themselves never probe: a host that uses the direct entries without either call gets the
+ * two-hop form wherever FORM would have said 3 (another fixed summation order, the same totals to fp64 rounding).  Ask FORM once before the first launch. */
+long long clhip_stage_train_query(int what, int N, int C);
+int clhip_stage_train_status(void* xch);
+int clhip_stage_train_fwd(const void* x, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
+                          float* const* rm, float* const* rv, float* const* mean, float* const* invstd, float* const* coef, void* const* z, void* const* y,
+                          void* const* mask, float momentum, float eps, void* xch, int trace, int entry, float* feat, int dtype, void* stream);
+int clhip_stage_train_bwd(const void* x, const void* dy, void* dx, int dx_accumulate, int N, int H, int W, int C, int nconv, const void* const* wd,
+                          const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* invstd, const void* const* z,
+                          const void* const* y, float* const* dgamma, float* const* dbeta, float* const* slab, void* const* dzg, void* xch, int trace, int entry,
+                          const float* dfeat, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Heads and losses (fp32).
  * linear: out[B,O] = x[B,D] W[O,D]^T + b   (nn.Linear heads: ewc.py:50, lwf.py:29-40, icarl.py:31)      */

@@ -140,6 +140,10 @@ _PROTOS = {
     "clhip_plan_read_act": (_i, [_p, _p, _i, _i, _p, _p]),
     "clhip_stage_eval_supported": (_i, [_i] * 5),
     "clhip_stage_eval": (_i, [_p, _p] + [_i] * 5 + [_p] * 5 + [_f, _i, _p]),
+    "clhip_stage_train_query": (C.c_longlong, [_i, _i, _i]),
+    "clhip_stage_train_status": (_i, [_p]),
+    "clhip_stage_train_fwd": (_i, [_p] + [_i] * 5 + [_p] * 11 + [_f, _f, _p, _i, _i, _p, _i, _p]),
+    "clhip_stage_train_bwd": (_i, [_p, _p, _p] + [_i] * 6 + [_p] * 11 + [_p, _i, _i, _p, _i, _p]),
     "clhip_linear_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "clhip_linear_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_ce_slice": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _i, _p, _i, _p, _p, _p]),

@@ -150,7 +150,7 @@ int clhip_shortcut_dgrad(const void* dz, const void* w_dg, void* dx, int accumul
 int clhip_stage_eval_launch(const void* x, void* y, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
                             const float* const* mean, const float* const* var, float eps, int dtype, hipStream_t st);
 
-// ---- stage_train.hip
+// ---- stage_train.hip (its direct entries clhip_stage_train_fwd / _bwd / _query / _status are part of the C ABI: include/clhip.h)
 int clhip_stage_train_max_batch();
 bool clhip_stage_train_supported(int N, int H, int W, int C, int nconv, int dtype);
 size_t clhip_stage_train_xch_bytes(int N);
@@ -162,7 +162,7 @@ int clhip_stage_train_fwd_launch(const void* x, int N, int H, int W, int C, int 
 int clhip_stage_train_bwd_launch(const void* x, const void* dy, void* dx, int dx_accumulate, int N, int H, int W, int C, int nconv, const void* const* wd,
                                  const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* invstd, const void* const* z,
                                  const void* const* y, float* const* dgamma, float* const* dbeta, float* const* slab, void* const* dzg, void* xch, int trace, int entry, const float* dfeat, int dtype, hipStream_t st);
-int clhip_stage_train_status(void* xch);
+int clhip_stage_train_status(void* xch);      // (plan.hip's use of it; the C ABI declares it first, so this keeps its C linkage)
 int clhip_stage_train_trace(void* xch, unsigned long long* out24);
 
 // ---- stem.hip: <= 8 padded input channels, 3x3

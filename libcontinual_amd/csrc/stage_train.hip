@@ -10,7 +10,7 @@
 //    (fp32, from the fp32 accumulators as the per-unit kernels take them) go through the in-launch all-reduce of xch.h -- two hops of tagged 8-byte
 //    granules, fp64 totals in ONE fixed order, identical in every workgroup -- so a run is bit-reproducible and independent of workgroup placement;
 //  * the forward leaves what the per-unit forward leaves: z of every convolution, mean / invstd / scale / shift and the running statistics of every
-//    BatchNorm, the activation + packed ReLU mask of every block output; the activation between the two convolutions of a block is NOT written (the
+//    BatchNorm, the activation of every block output (NOT its packed ReLU mask: the backward of either path takes that mask from y > 0); the activation between the two convolutions of a block is NOT written (the
 //    backward recomputes it from z, as the per-unit "lazy" path does).  Either backward can therefore follow either forward.
 #include <stdlib.h>
 
@@ -38,7 +38,7 @@ struct StConv {
     float* coef;              // [2][C] scale, shift
     bf16_t* z;                // [N][HW][HW][C] pre-BatchNorm output
     bf16_t* y;                // block outputs (second convolution of a block): the activation; nullptr for the first convolution of a block
-    unsigned char* mask;      // ... and its packed ReLU mask (bit e of byte i = element 8 i + e > 0), or nullptr
+    unsigned char* mask;      // (carried for the plan's table layout; no kernel here reads or writes it: a block output's ReLU mask is y > 0)
 };
 
 struct StFwdParams {
@@ -1606,11 +1606,46 @@ int clhip_stage_train_bwd_launch(const void* x, const void* dy, void* dx, int dx
 }
 
 // the sticky error word of an exchange buffer (non-zero: a bounded spin ran out -- the grid was not co-resident); synchronises the device
-int clhip_stage_train_status(void* xch) {
+extern "C" int clhip_stage_train_status(void* xch) {
     unsigned ctl[4] = {0, 0, 0, 0};
     if (xch == nullptr) return 0;
     if (hipMemcpy(ctl, xch, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (int)ctl[1];
+}
+
+// ---- the direct entries (include/clhip.h): the two launchers as they are, for callers that own their buffers -- the same `supported` checks, the same CLHIP_EINVAL
+extern "C" int clhip_stage_train_fwd(const void* x, int N, int H, int W, int C, int nconv, const void* const* w, const float* const* gamma, const float* const* beta,
+                                     float* const* rm, float* const* rv, float* const* mean, float* const* invstd, float* const* coef, void* const* z, void* const* y,
+                                     void* const* mask, float momentum, float eps, void* xch, int trace, int entry, float* feat, int dtype, void* stream) {
+    CLHIP_CHECK_ARG(x && w && gamma && beta && rm && rv && mean && invstd && coef && z && y && mask);
+    return clhip_stage_train_fwd_launch(x, N, H, W, C, nconv, w, gamma, beta, rm, rv, mean, invstd, coef, z, y, mask, momentum, eps, xch, trace, entry, feat, dtype, (hipStream_t)stream);
+}
+
+extern "C" int clhip_stage_train_bwd(const void* x, const void* dy, void* dx, int dx_accumulate, int N, int H, int W, int C, int nconv, const void* const* wd,
+                                     const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* invstd, const void* const* z,
+                                     const void* const* y, float* const* dgamma, float* const* dbeta, float* const* slab, void* const* dzg, void* xch, int trace, int entry,
+                                     const float* dfeat, int dtype, void* stream) {
+    CLHIP_CHECK_ARG(x && (dy || dfeat) && dx && wd && gamma && beta && mean && invstd && z && y && dgamma && dbeta && slab && dzg);
+    return clhip_stage_train_bwd_launch(x, dy, dx, dx_accumulate, N, H, W, C, nconv, wd, gamma, beta, mean, invstd, z, y, dgamma, dbeta, slab, dzg, xch, trace, entry, dfeat, dtype,
+                                        (hipStream_t)stream);
+}
+
+// what a launch of N workgroups at C channels would do, from the predicates the launchers and the kernels use themselves.  CLHIP_STAGE_TRAIN_Q_FORM runs the XCD probe
+// where this device's answer is not cached yet: never call it inside a stream capture.
+extern "C" long long clhip_stage_train_query(int what, int N, int C) {
+    switch (what) {
+    case CLHIP_STAGE_TRAIN_Q_MAX_BATCH: return clhip_stage_train_max_batch();
+    case CLHIP_STAGE_TRAIN_Q_XCH_BYTES: return N >= 1 ? (long long)clhip_stage_train_xch_bytes(N) : -1;
+    case CLHIP_STAGE_TRAIN_Q_SLAB_BLOCKS: return (N >= 1 && (C == 16 || C == 32 || C == 64)) ? clhip_stage_train_slab_blocks(N, C) : -1;
+    case CLHIP_STAGE_TRAIN_Q_GROUP: return (N >= 1 && (C == 16 || C == 32 || C == 64)) ? (stage_train_group(N, C) ? 1 : 0) : -1;
+    case CLHIP_STAGE_TRAIN_Q_FORM: {
+        if (N < 1 || !(C == 16 || C == 32 || C == 64)) return -1;
+        const int NV = 2 * C;                                       // (sum, sum of squares / sum g, sum g xhat) per channel: what every exchange of both kernels carries
+        if (clhip_stage_train_xcd_rule(true) && xch_hier(N, NV)) return 3;      // (the launchers keep XchBuf::gx only where the rule holds: xch_begin / xch_end)
+        return xch_one_hop(N, NV) ? 1 : 2;
+    }
+    default: return -1;
+    }
 }
 
 // the phase stamps of the last traced launches (STAGE_TRACE): 24 64-bit tick counts (100 MHz); synchronises the device

@@ -169,7 +169,7 @@ __device__ __forceinline__ void xch_sweep(const XchBuf& b, int G, int NV, unsign
     }
     __syncthreads();
 }
-__device__ __forceinline__ bool xch_one_hop(int G, int NV) { return G * NV <= kXchOneHop; }
+__host__ __device__ __forceinline__ bool xch_one_hop(int G, int NV) { return G * NV <= kXchOneHop; }
 
 // THREE levels for big grids (round 6, late): a granule that only has to reach the OTHER workgroups of the same XCD need not be written through to memory -- they
 // share the L2.  Measured (tools/ubench/xcd_local.hip): a workgroup of a grid of any size lands on XCD blockIdx % 8; a round trip between two workgroups of one XCD
@@ -183,7 +183,7 @@ __device__ __forceinline__ bool xch_one_hop(int G, int NV) { return G * NV <= kX
 // placement rule above: a workgroup whose XCD is not blockIdx % 8 would poll an L2 its partners never write -- the bounded spins turn that into the error word, and
 // stage_train.hip checks the rule once per device before it lets a plan use this form (clhip_stage_train_xcd_rule).
 constexpr int kXchXcds = 8;
-__device__ __forceinline__ bool xch_hier(int G, int NV) { return G * NV > kXchOneHop && G >= 64; }
+__host__ __device__ __forceinline__ bool xch_hier(int G, int NV) { return G * NV > kXchOneHop && G >= 64; }
 __device__ __forceinline__ void xch_store_local(unsigned long long* p, unsigned tag, unsigned value) {
     __hip_atomic_store((xch_gu64*)p, ((unsigned long long)tag << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // no cache bits: stays in the XCD's L2
 }

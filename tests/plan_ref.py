@@ -365,8 +365,9 @@ def z_link(units, i, D, dt):
     return ref, bound, acc
 
 
-def judge(units, D, dt, pool_win, nbt=None):
-    """every link of one training pass (see the module docstring) -> Verdict"""
+def judge(units, D, dt, pool_win, nbt=None, forward_only=False):
+    """every link of one training pass (see the module docstring) -> Verdict.  forward_only: the links of the forward alone (z, the statistics, y, feat) -- for a
+    plan whose backward keeps the gradients of its activations in LDS (the stage-level training launches), where D holds no dy"""
     V = Verdict()
     n = len(units)
     kind = "rsqrt" if dt == "bf16" else "fp64"
@@ -418,6 +419,8 @@ def judge(units, D, dt, pool_win, nbt=None):
     V.add(n, "feat", D["feat"], reff, B.bound_pool_fwd(feat_of(ylast.abs(), pool_win) * hw, hw, reff))
     if nbt is not None:
         V[(n, "num_batches_tracked")] = 0.0 if all(int(v) == nbt[0] for v in nbt[1]) else float("inf")
+    if forward_only:
+        return V
     # ---- backward: unit by unit in reverse; DZ[i] = (reference, bound) of the unseen dz; contrib[a] = the writes of activation a + 1's gradient in sweep order
     DZ = [None] * n
     RAWG = [None] * n                                            # (reference, bound) of the raw-gradient buffer of unit i

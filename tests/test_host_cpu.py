@@ -30,6 +30,21 @@ def test_library_exports_every_header_symbol():
     assert _lib.lib().clhip_bn_bwd_ws_floats(1024, 64) > 0
 
 
+def test_stage_train_entries_are_declared_bound_and_answer_host_queries():
+    """the direct entries of the stage-level training launches (csrc/stage_train.hip): in the header, in _lib._PROTOS, and the parts of the query that need no device"""
+    declared = _lib.header_symbols()
+    for n in ("clhip_stage_train_fwd", "clhip_stage_train_bwd", "clhip_stage_train_query", "clhip_stage_train_status"):
+        assert n in declared and n in _lib._PROTOS, n
+    assert len(_lib._PROTOS["clhip_stage_train_fwd"][1]) == 25 and len(_lib._PROTOS["clhip_stage_train_bwd"][1]) == 26
+    q = _lib.lib().clhip_stage_train_query
+    Q_XCH, Q_SLAB, Q_GROUP = 1, 2, 3                               # include/clhip.h: CLHIP_STAGE_TRAIN_Q_*
+    assert [q(Q_GROUP, n, c) for n, c in ((127, 64), (128, 64), (256, 32), (256, 16))] == [0, 1, 0, 0]
+    assert [q(Q_SLAB, n, c) for n, c in ((127, 64), (128, 64), (130, 64), (130, 32), (5, 16))] == [127, 8, 9, 130, 5]
+    assert 0 < q(Q_XCH, 1, 0) < q(Q_XCH, 65, 0) < q(Q_XCH, 256, 0) and q(Q_XCH, 0, 0) == -1
+    assert q(99, 1, 16) == -1 and q(Q_SLAB, 3, 48) == -1 and q(Q_GROUP, 3, 48) == -1 and q(Q_GROUP, 0, 64) == -1
+    assert _lib.lib().clhip_stage_train_status(None) == 0          # (no buffer, no word)
+
+
 def test_library_exports_nothing_outside_the_header():
     """the product's behaviour has to be a function of include/clhip.h -- every unmangled `clhip_*` export of the shared
     library is declared there (tuning and ablation hooks included: they go through clhip_config)"""

@@ -55,7 +55,8 @@ def _forward_reads(bb, x, flag):
     return f, z, y, stats1
 
 
-@pytest.mark.parametrize("kind,batch", [("cifar", 32), ("cifar", 256), ("cifar", 100), ("v2", 64)])
+# (200: the group weight gradient's last group is ragged, 12 full groups + 8 images; 48: the 64-channel run takes the two-hop exchange under the default switches)
+@pytest.mark.parametrize("kind,batch", [("cifar", 32), ("cifar", 256), ("cifar", 100), ("v2", 64), ("cifar", 200), ("cifar", 48)])
 def test_stage_level_training_forward_matches_the_per_unit_launches(kind, batch):
     bb = _backbone(kind, 3)
     _trained_like(bb, 4)
@@ -112,7 +113,7 @@ def _rel(a, b):
     return float((a - b).norm()) / max(float(b.norm()), 1e-12)
 
 
-@pytest.mark.parametrize("kind,batch", [("cifar", 32), ("cifar", 256), ("cifar", 72), ("v2", 128)])
+@pytest.mark.parametrize("kind,batch", [("cifar", 32), ("cifar", 256), ("cifar", 72), ("v2", 128), ("cifar", 200), ("cifar", 48)])
 def test_stage_level_training_backward_matches_the_per_unit_launches(kind, batch):
     bb = _backbone(kind, 7)
     _trained_like(bb, 8)
@@ -240,3 +241,20 @@ def test_a_forward_no_backward_follows_leaves_the_same_features_and_statistics(k
     bb._stats.copy_(stats0)
     fb, gb = _step(bb, x, w, b"1", b"1")
     assert torch.equal(fa, fb) and torch.equal(ga, gb)
+
+
+def test_the_default_threshold_lies_between_batch_64_and_65(monkeypatch):
+    """STAGE_TRAIN unset: a training forward of 65 images makes the three stage-level launches, one of 64 images none (plan.hip: stage_train_default)"""
+    monkeypatch.delenv("CLHIP_STAGE_TRAIN", raising=False)
+    assert _lib.lib().clhip_config(b"STAGE_TRAIN", None) == 0
+    bb = _backbone("cifar", 41)
+    made = {}
+    for batch in (65, 64):
+        x = torch.randn(batch, 3, 32, 32, generator=torch.Generator().manual_seed(42)).cuda()
+        n0 = _launches(bb)
+        bb(x)["features"].sum().backward()
+        torch.cuda.synchronize()
+        n1 = _launches(bb)
+        made[batch] = (n1[1] - n0[1], n1[2] - n0[2])
+    assert _status(bb) == [0] * len(bb._handle.plans)
+    assert made == {65: (3, 3), 64: (0, 0)}, made
