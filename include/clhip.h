@@ -1020,6 +1020,41 @@ int clhip_class_moments(const float* F, const int32_t* offsets, float* mean, flo
 int clhip_ca_sample(const float* mean, const float* scale, const float* chol, const float* Z, const int64_t* dest, float* X, int64_t* labels, int C,
                     int S, int D, int64_t class_lo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RAPF's adapter step (core/model/rapf.py; csrc/rapf.hip) under the same rules: fp32 in / fp32 accumulate, the matrix-shaped products on the f32-input
+ * MFMA, row-major and dense, no atomics, every sum in an order fixed by the shapes (two calls give the same bits), every output WRITTEN.
+ * Notation: X [R, E] the step's rows, R = B + M + Q: B image rows | M replay rows | Q edge rows; W [E, E] the adapter in nn.Linear layout (out x in);
+ * T [C, E] the text rows, ALREADY L2-normalised (they are not normalised again); scale = exp(logit_scale).
+ * rapf_draw    : sample() (rapf.py:37-44) as called from :318-322 and :328-334.  G groups; group g draws cnt[g] rows of class cls[g]:
+ *                X[row0 + r, j] = mean[cls[g], j] + sum_{k <= j} Z[r, k] * chol[cls[g], j, k], r counting through the groups in order.  mean [Cs, E],
+ *                chol [Cs, E, E] (lower, row-major, one factor per STORED class: the covariance does not change after after_task, so it is factored there,
+ *                not in every step as :41 does), Z [sum cnt, E] standard normals.  The draws land behind the image rows of the step's row matrix: nothing
+ *                is concatenated, and rows outside [row0, row0 + sum cnt) are untouched.  A class may appear in several groups and the counts may
+ *                differ.  The strict upper triangle of chol is never read.  cls / cnt are HOST arrays (int32 [G]): a class outside [0, Cs) or a count
+ *                < 1 returns CLHIP_EINVAL before any launch, with no synchronisation; the table travels in the kernel arguments (128 groups per launch).
+ * rapf_step_fwd: ClassIncrementalCLIP.forward (:143-153) and the losses (:341-353).  A = X W^T, n_r = A_r / |A_r| -- NO eps, as in the reference: a zero
+ *                row gives inf / NaN and is the caller's problem.  Rows r < B + M: logits[r, c] = scale * n_r . T_c and the mean over those rows of
+ *                CE(logits_r, labels[r]) is loss_c.  Edge row q (r = B + M + q): h_q = relu(margin - n . T[pos[q]] + n . T[neg[q]]) (margin 0.1 at
+ *                :348), loss_h = mean_q h_q.  The reference's second normalisation of the edge and text rows (:343-347) is the identity on unit
+ *                vectors, in value and in Jacobian, and is done once.  Outputs: logits [B + M, C]; n [R, E]; loss [3] = (loss_c + loss_h if Q > 0
+ *                else loss_c, loss_c, loss_h); row_loss [R] (the CE term of a row, h_q of an edge row); pred int64 [B] (argmax of the image rows, ties to
+ *                the lower index); correct int32 [1] (nullable); and G [R, E] = dloss/dA:
+ *                    g_n = scale / (B + M) * (softmax - onehot) . T on CE rows, 1[h_q > 0] / Q * (T[neg] - T[pos]) on edge rows (h_q == 0: 0, torch's relu),
+ *                    G_r = (g_n - n_r (n_r . g_n)) / |A_r|.
+ *                labels int64 [B + M], pos / neg int64 [Q] live on the device.  A label outside [0, C) is treated as clhip_ce_slice treats one outside its
+ *                slice: no loss term, no onehot in the gradient (the softmax part stays), never counted correct.  An edge pair with pos or neg outside
+ *                [0, C) is inactive: h_q = 0 and G_r = 0.  M = 0 and Q = 0 are ordinary cases (pos / neg may then be NULL).
+ *                INFERENCE form: labels == NULL (then M = Q = 0): only logits and n are written; G, row_loss, loss, pred, correct may be NULL.
+ *                2 E + C <= 8192 (one row of n, g_n and the logits in LDS).
+ * rapf_step_bwd: dW [E, E] = g * G^T X, dW[o, i] = g * sum_r G[r, o] * X[r, i] with r ascending inside one workgroup per tile (no slabs at R of a few
+ *                hundred); g is the upstream scalar. */
+int clhip_rapf_draw(const float* mean, const float* chol, const float* Z, float* X, const int32_t* cls, const int32_t* cnt, int G, int Cs, int E, int row0,
+                    void* stream);
+int clhip_rapf_step_fwd(const float* X, const float* W, const float* T, const int64_t* labels /*nullable*/, const int64_t* pos /*nullable*/,
+                        const int64_t* neg /*nullable*/, float scale, float margin, float* logits, float* n, float* G, float* row_loss, float* loss,
+                        int64_t* pred, int32_t* correct /*nullable*/, int B, int M, int Q, int E, int C, void* stream);
+int clhip_rapf_step_bwd(const float* G, const float* X, float g, float* dW, int R, int E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

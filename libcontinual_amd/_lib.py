@@ -252,6 +252,9 @@ _PROTOS = {
     "clhip_rp_classify": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clhip_class_moments": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "clhip_ca_sample": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _p]),
+    "clhip_rapf_draw": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "clhip_rapf_step_fwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "clhip_rapf_step_bwd": (_i, [_p, _p, _f, _p, _i, _i, _p]),
 }
 
 _CHECKED = {}

@@ -144,29 +144,6 @@ __global__ __launch_bounds__(kThreads) void ca_cov_kernel(const float* __restric
         }
 }
 
-// Operand<false>::fetch for a lower-triangular operand: row j is read up to k = j only
-__device__ __forceinline__ void fetch_lower(const float* __restrict__ p, size_t ld, int J, int kend, int j0, int k0, bool vec, float4 (&r)[2]) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        const int j = j0 + (t >> 2) + 64 * h, k = k0 + (t & 3) * 4;
-        if (j < J) {
-            const int ke = min(kend, j + 1);
-            const float* q = p + (size_t)j * ld + k;
-            if (vec && k + 4 <= ke) {
-                const float4 u = *reinterpret_cast<const float4*>(q);
-                v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (k + e < ke) v[e] = q[e];
-            }
-        }
-        r[h] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
 // X[dest[c S + s], j] = scale[c] mean[c, j] + sum_{k <= j} Z[c S + s, k] L[c, j, k]; blockIdx = (column tile, row tile, class)
 __global__ __launch_bounds__(kThreads) void ca_sample_kernel(const float* __restrict__ mean, const float* __restrict__ scale, const float* __restrict__ chol,
                                                               const float* __restrict__ Z, const int64_t* __restrict__ dest, float* __restrict__ X,

@@ -142,7 +142,9 @@ def get_dataloader(config, mode, cls_map=None, device=None):
     """class order: `class_order` key if present else np.random.permutation (seeded by init_seed ->
     the seed-1993 PyCIL order), reference dataloader.py:113-122"""
     data_root = config["data_root"]
-    if f"{mode}_trfms" in config:
+    if config.get("is_rapf"):
+        trfms = T.rapf_transform(config["image_size"])                   # RAPF's fixed CLIP preprocessing, both modes (dataloader.py:41-53)
+    elif f"{mode}_trfms" in config:
         trfms = T.create_transforms(config[f"{mode}_trfms"])            # YAML-declared pipeline (dataloader.py:54-55)
     else:
         trfms = T.default_transform(config, mode)                         # per-dataset defaults (dataloader.py:57-74)

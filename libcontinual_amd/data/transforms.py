@@ -212,6 +212,15 @@ def imagenet_resnet_transform(mode, size, resize, mean, std):
     return Compose([Resize(resize), CenterCrop(size), *common])
 
 
+CLIP_MEAN, CLIP_STD = [0.48145466, 0.4578275, 0.40821073], [0.26862954, 0.26130258, 0.27577711]
+
+
+def rapf_transform(image_size):
+    """`is_rapf: true` (get_augment, core/data/dataloader.py:41-53): CLIP's preprocessing for train and test alike -- bicubic Resize(n_px), CenterCrop(n_px),
+    RGB (a grey image is repeated to three channels where it is read, _to_hwc_u8), ToTensor, CLIP's mean / std.  It overrides any `*_trfms` of the config."""
+    return Compose([Resize(image_size, interpolation="BICUBIC"), CenterCrop(image_size), ToTensor(), Normalize(CLIP_MEAN, CLIP_STD)])
+
+
 def default_transform(config, mode):
     """the pipeline of a config without `{mode}_trfms`: imagenet-r -> RandomResizedCrop(224) / Resize(256) + CenterCrop(224), tiny-imagenet -> the
     64 x 64 equivalents (data.py:121-137, 191-211); every other dataset (cifar*, synthetic, ...) keeps cifar_resnet_transform, and so does any ViT"""

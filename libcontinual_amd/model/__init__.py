@@ -18,4 +18,5 @@ from .sd_lora import SD_LoRA  # noqa: F401
 from .lora_sub import LoRAsub_DRS  # noqa: F401
 from .codaprompt import CodaPrompt  # noqa: F401
 from .dualprompt import DualPrompt  # noqa: F401
+from .rapf import RAPF  # noqa: F401
 from .heads import HipLinear  # noqa: F401

@@ -552,6 +552,98 @@ def ca_sample(mean, scale, chol, z, dest, class_lo):
     return X, labels
 
 
+# ------------------------------------------------------------------------------------------ RAPF's adapter step (csrc/rapf.hip)
+def rapf_draw(mean, chol, z, X, row0, cls, cnt):
+    """X[row0 + r] = mean[cls[g]] + z[r] @ chol[cls[g]]^T for the rows r of group g, cnt[g] rows each, groups back to back (sample(), rapf.py:37-44): the
+    draws are written into the step's row matrix `X` in place.  `cls` / `cnt` are host sequences; `chol` [Cs, E, E] is read on and below the diagonal only."""
+    import ctypes as C
+    if not (mean.dtype == chol.dtype == z.dtype == X.dtype == torch.float32 and all(t.is_contiguous() for t in (mean, chol, z, X))):
+        raise _lib.ClhipError("rapf_draw: mean, chol, z and X must be contiguous fp32 (X is written in place)")
+    _dev(mean, chol, z, X)
+    G, (Cs, E) = len(cls), mean.shape
+    n = int(sum(int(c) for c in cnt))
+    if len(cnt) != G or tuple(chol.shape) != (Cs, E, E) or tuple(z.shape) != (n, E) or X.dim() != 2 or X.shape[1] != E or row0 < 0 or row0 + n > X.shape[0]:
+        raise _lib.ClhipError(f"rapf_draw: {G} groups of {n} rows at row {row0}; mean {tuple(mean.shape)}, chol {tuple(chol.shape)}, z {tuple(z.shape)}, "
+                              f"X {tuple(X.shape)} do not fit")
+    call("clhip_rapf_draw", _ptr(mean), _ptr(chol), _ptr(z), _ptr(X), (C.c_int32 * G)(*[int(c) for c in cls]), (C.c_int32 * G)(*[int(c) for c in cnt]), G, Cs, E,
+         int(row0), _st())
+    return X
+
+
+class RapfStep:
+    """what clhip_rapf_step_fwd wrote: logits [B + M, C], n [R, E], G = dloss/dA [R, E], row_loss [R], loss [3] = (loss, loss_c, loss_h), pred [B], correct [1]"""
+    __slots__ = ("logits", "n", "G", "row_loss", "loss", "pred", "correct")
+
+
+def rapf_step_fwd(X, W, T, scale, labels=None, pos=None, neg=None, B=None, margin=0.1):
+    """One adapter step of RAPF without autograd (rapf.py:143-153, :341-353): rows X [R, E] = [B image | M replay | Q edge], adapter W [E, E], normalised text
+    rows T [C, E].  labels int64 [B + M]; pos / neg int64 [Q] (Q = 0: None).  labels None: the inference form (logits and n only, every row an image row)."""
+    X, W, T = _f32c(X), _f32c(W), _f32c(T)
+    R, E = X.shape
+    Cn = T.shape[0]
+    out = RapfStep()
+    if labels is None:
+        B, M, Q = R, 0, 0
+    else:
+        labels = labels.to(device=X.device, dtype=torch.int64).contiguous()
+        Q = 0 if pos is None else int(pos.numel())
+        B = labels.numel() if B is None else int(B)
+        M = labels.numel() - B
+        if Q:
+            pos, neg = pos.to(device=X.device, dtype=torch.int64).contiguous(), neg.to(device=X.device, dtype=torch.int64).contiguous()
+        else:
+            pos = neg = None
+    _dev(X, W, T, labels, pos, neg)
+    if tuple(W.shape) != (E, E) or T.shape[1] != E or B < 1 or M < 0 or B + M + Q != R or (Q and neg.numel() != Q):
+        raise _lib.ClhipError(f"rapf_step_fwd: X {tuple(X.shape)}, W {tuple(W.shape)}, T {tuple(T.shape)}, B {B}, M {M}, Q {Q} do not fit")
+    f = dict(device=X.device, dtype=torch.float32)
+    out.logits, out.n = torch.empty(B + M, Cn, **f), torch.empty(R, E, **f)
+    out.G = out.row_loss = out.loss = out.pred = out.correct = None
+    if labels is not None:
+        out.G, out.row_loss, out.loss = torch.empty(R, E, **f), torch.empty(R, **f), torch.empty(3, **f)
+        out.pred, out.correct = torch.empty(B, device=X.device, dtype=torch.int64), torch.empty(1, device=X.device, dtype=torch.int32)
+    call("clhip_rapf_step_fwd", _ptr(X), _ptr(W), _ptr(T), _ptr(labels), _ptr(pos), _ptr(neg), float(scale), float(margin), _ptr(out.logits), _ptr(out.n),
+         _ptr(out.G), _ptr(out.row_loss), _ptr(out.loss), _ptr(out.pred), _ptr(out.correct), B, M, Q, E, Cn, _st())
+    return out
+
+
+def rapf_step_bwd(G, X, g=1.0):
+    """dW [E, E] = g * G^T X: the adapter's weight gradient from G = dloss/dA of rapf_step_fwd"""
+    G, X = _f32c(G), _f32c(X)
+    _dev(G, X)
+    R, E = X.shape
+    if tuple(G.shape) != (R, E):
+        raise _lib.ClhipError(f"rapf_step_bwd: G {tuple(G.shape)} and X {tuple(X.shape)} differ")
+    dW = torch.empty(E, E, device=X.device, dtype=torch.float32)
+    call("clhip_rapf_step_bwd", _ptr(G), _ptr(X), float(g), _ptr(dW), R, E, _st())
+    return dW
+
+
+class _RapfLossFn(torch.autograd.Function):
+    """the step's loss as a tensor whose backward is clhip_rapf_step_bwd into the adapter's weight.  The trainer's cached unit root gradient (UNIT_GRAD_PTRS)
+    is taken as g = 1 without looking at it; any other upstream gradient is read on the host (one synchronisation)."""
+
+    @staticmethod
+    def forward(ctx, W, X, T, scale, labels, pos, neg, B, margin, holder):
+        st = rapf_step_fwd(X, W.detach(), T, scale, labels, pos, neg, B, margin)
+        holder.append(st)
+        ctx.save_for_backward(st.G, X)
+        return st.loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        G, X = ctx.saved_tensors
+        g = 1.0 if dloss.data_ptr() in UNIT_GRAD_PTRS else float(dloss)
+        return (rapf_step_bwd(G, X, g),) + (None,) * 9
+
+
+def rapf_loss(W, X, T, scale, labels, pos=None, neg=None, B=None, margin=0.1):
+    """(loss, RapfStep): loss = loss_c (+ loss_h with edge rows), differentiable w.r.t. the adapter weight W only"""
+    holder = []
+    loss = _RapfLossFn.apply(W, _f32c(X), T, scale, labels, pos, neg, B, margin, holder)
+    return loss, holder[0]
+
+
 def head_sgd_step(x, y, w, b, mom_w, mom_b, lr, momentum, weight_decay, ws=None):
     """one SGD step of a linear head on the mean cross-entropy of (x [B, D], y [B]) without autograd: clhip_linear_fwd, clhip_ce_window (loss and
     d loss / d logits), clhip_linear_bwd, clhip_sgd_step_multi -- four launches, w [O, D] / b [O] and their momentum buffers updated in place

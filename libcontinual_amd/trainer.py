@@ -438,6 +438,8 @@ class Trainer:
         acc_table = np.zeros((T, T))
         bwt_list, frgt_list = [], []
         model = self.model
+        if hasattr(model, "set_class_names"):             # core/trainer.py:280-281: RAPF builds its prompts from the train loader's label -> name map
+            model.set_class_names(getattr(self.train_loader, "cls_map", None))
         for task_idx in range(T):
             self.task_idx = task_idx
             self.log(f"================Task {task_idx} Start!================")
